@@ -15,6 +15,12 @@ of ricepp/ricepp_benchmark.cpp:145-146,155-156 applied to the round trip.
 
 Launch:  python bench.py [--gpus N --steps K --warmup W] [--workload mix]
          (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds what takes runs of its own: the per-kernel event timings and the
+roofline block they feed, the device-copy rate and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs below), for comparing two builds output for output.
 """
 
 from __future__ import annotations
@@ -204,6 +210,56 @@ def profiled_counters(kernel: str, profile: str = "pmc_latest.json"):
                          f"which no bench workload launches)"
 
 
+DUMP_SAMPLE = 1 << 22  # elements of a sampled array: two of them in float32 are 32 MiB, under the 64 MB a dump may take
+DUMP_SEED = 20240611
+
+
+def _dump_indices(total: int) -> np.ndarray:
+    """Every index below `total`, or a fixed sorted sample of DUMP_SAMPLE of them (seeded: the same indices
+    for the same total, whatever the build)."""
+    if total <= DUMP_SAMPLE:
+        return np.arange(total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(pipe, out_dir: Path, rank: int = 0, world: int = 1) -> None:
+    """What a caller of ShardPipeline.step() receives, as it stands after the last step, one .npy each
+    (rank r of several writes <name>.rank<r>.npy):
+      sizes          encoded bytes per block (float64)
+      image_offsets  byte offset of every block in the concatenated image, all ranks (float64)
+      enc_status, dec_status  per-block codec status (float32)
+      encoded        bytes of this rank's blocks laid end to end without the capacity gaps between them
+                     (float32): all of them, or the bytes at a fixed seeded sample of positions
+      decoded        the decoded samples as the int16 words in memory (float32): all, or a seeded sample
+    Only the first sizes[i] bytes of a block's capacity are written by the encoder, so nothing else of the
+    encode buffer is read here."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+
+    def save(name: str, a: np.ndarray) -> None:
+        np.save(out_dir / f"{name}{suffix}.npy", a)
+
+    dev = pipe.data.device
+    sizes = pipe.sizes.cpu().numpy()
+    save("sizes", sizes.astype(np.float64))
+    save("image_offsets", pipe.image_offsets.cpu().numpy().astype(np.float64))
+    save("enc_status", pipe.enc_status.cpu().numpy().astype(np.float32))
+    save("dec_status", pipe.dec_status.cpu().numpy().astype(np.float32))
+    # position p of the gap-free image lies in block b = the last one starting at or before p
+    starts = np.zeros(len(sizes), np.int64)
+    if len(sizes):
+        starts[1:] = np.cumsum(sizes)[:-1]
+    pos = _dump_indices(int(sizes.sum()))
+    if len(pos):
+        b = np.searchsorted(starts, pos, side="right") - 1
+        where = torch.as_tensor(pipe.out_offsets[b] + (pos - starts[b]), device=dev)
+        save("encoded", pipe.data[where].cpu().numpy().astype(np.float32))
+    else:
+        save("encoded", np.zeros(0, np.float32))
+    where = torch.as_tensor(_dump_indices(pipe.total_samples), device=dev)
+    save("decoded", pipe.decoded[where].cpu().numpy().astype(np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -221,7 +277,15 @@ def main() -> None:
     ap.add_argument("--mix-gib", type=int, default=32, help="total size of the configs[3] mix")
     ap.add_argument("--decode-path", choices=("auto", "fused", "segmented"), default="auto",
                     help="force a decode path (A/B measurements; the default is the library's own choice)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel event timings and the roofline block, "
+                         "the device-copy rate, the CPU baseline (--no-cpu, --cpu-seconds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / "
+                         "float64; large arrays as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -297,15 +361,20 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # per-kernel timing with events on the launch stream (torch's current stream)
-    k_enc, k_dec = pipe.kernel_times(iters=max(5, args.steps))
+    # the buffers still hold the last timed step's results: written before anything launches again
+    if args.dump_outputs is not None:
+        dump_outputs(pipe, args.dump_outputs, rank, world)
+
     comp_bytes = int(pipe.enc.sizes.sum().item())
     raw_bytes = shard_bytes
-    enc_bytes = raw_bytes + comp_bytes + 8 * nblocks
-    dec_bytes = comp_bytes + raw_bytes
-    dominant = "decode" if k_dec >= k_enc else "encode"
-    kt, kb = (k_dec, dec_bytes) if dominant == "decode" else (k_enc, enc_bytes)
-    achieved = kb / kt / 1e9
+    if args.full:
+        # per-kernel timing with events on the launch stream (torch's current stream)
+        k_enc, k_dec = pipe.kernel_times(iters=max(5, args.steps))
+        enc_bytes = raw_bytes + comp_bytes + 8 * nblocks
+        dec_bytes = comp_bytes + raw_bytes
+        dominant = "decode" if k_dec >= k_enc else "encode"
+        kt, kb = (k_dec, dec_bytes) if dominant == "decode" else (k_enc, enc_bytes)
+        achieved = kb / kt / 1e9
 
     if args.workload == "mix":
         t = torch.tensor([raw_bytes, comp_bytes], dtype=torch.float64, device=dev)
@@ -337,12 +406,16 @@ def main() -> None:
                 "bytes_total": int(total_raw),
                 "compression_ratio": round(total_comp / total_raw, 5),
                 "parallelism": f"shard{world} (byte-balanced contiguous block ranges, RCCL all-gather of encoded sizes)",
+            },
+        }
+        if args.full:
+            result["config"].update({
                 "rank0_encode_ms": round(k_enc * 1e3, 3),
                 "rank0_decode_ms": round(k_dec * 1e3, 3),
                 "rank0_encode_GiBps": round(raw_bytes / k_enc / 2**30, 2),
                 "rank0_decode_GiBps": round(raw_bytes / k_dec / 2**30, 2),
-            },
-            "roofline": {
+            })
+            result["roofline"] = {
                 "bound": "hbm",
                 "kernel": "rpp_decode_batch_ws (segmented: unit parse + extraction + fused short streams)",
                 "achieved": round(achieved, 1),
@@ -351,27 +424,21 @@ def main() -> None:
                 "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": None,
                 "traffic_source": "not profiled for the mix",
-            },
-        }
-        # (PMC of a 32 GiB mix: only at that size are the bytes per call this run's)
-        mc, msrc = profiled_counters("decode", "pmc_mix.json") if args.mix_gib == 32 and world == 1 else \
-            (None, "the PMC profile is of the 32 GiB mix on one GPU")
-        if mc and "hbm_bytes_per_call" in mc:
-            result["roofline"]["traffic"] = mc["hbm_bytes_per_call"]
-            result["roofline"]["traffic_source"] = msrc + ": every kernel of one decode call"
-            result["roofline"]["algorithmic_bytes"] = int(dec_bytes)
-        else:
-            result["roofline"]["traffic_source"] = msrc
+            }
+            # (PMC of a 32 GiB mix: only at that size are the bytes per call this run's)
+            mc, msrc = profiled_counters("decode", "pmc_mix.json") if args.mix_gib == 32 and world == 1 else \
+                (None, "the PMC profile is of the 32 GiB mix on one GPU")
+            if mc and "hbm_bytes_per_call" in mc:
+                result["roofline"]["traffic"] = mc["hbm_bytes_per_call"]
+                result["roofline"]["traffic_source"] = msrc + ": every kernel of one decode call"
+                result["roofline"]["algorithmic_bytes"] = int(dec_bytes)
+            else:
+                result["roofline"]["traffic_source"] = msrc
         if rank == 0:
             print(json.dumps(result), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
-
-    counters, traffic_src = profiled_counters(f"rpp_{dominant}_kernel")
-    traffic = counters.get("hbm_bytes_per_launch") if counters else None
-    # the launch's length in GPU cycles (GRBM_GUI_ACTIVE per XCD): the kernel's work, whatever the clock
-    kcycles = counters.get("cycles_per_launch") if counters else None
 
     total_bytes = raw_bytes * world * args.steps
     value = total_bytes / elapsed / 2**30
@@ -399,12 +466,20 @@ def main() -> None:
             "parallelism": f"shard{world} (blocks sharded, RCCL all-gather of encoded sizes)",
             "step_launch": ("HIP graph replay" + (" (encode | eager all-gather | scan + decode)" if world > 1 else "")
                             if graphed else "eager"),
+        },
+    }
+    if args.full:
+        counters, traffic_src = profiled_counters(f"rpp_{dominant}_kernel")
+        traffic = counters.get("hbm_bytes_per_launch") if counters else None
+        # the launch's length in GPU cycles (GRBM_GUI_ACTIVE per XCD): the kernel's work, whatever the clock
+        kcycles = counters.get("cycles_per_launch") if counters else None
+        result["config"].update({
             "encode_kernel_us": round(k_enc * 1e6, 2),
             "decode_kernel_us": round(k_dec * 1e6, 2),
             "encode_GiBps": round(raw_bytes / k_enc / 2**30, 2),
             "decode_GiBps": round(raw_bytes / k_dec / 2**30, 2),
-        },
-        "roofline": {
+        })
+        result["roofline"] = {
             "bound": "hbm",
             "kernel": f"rpp_{dominant}_kernel",
             "achieved": round(achieved, 1),
@@ -416,9 +491,8 @@ def main() -> None:
             "kernel_cycles_per_launch": kcycles,
             "kernel_clock_GHz": round(kcycles / kt / 1e9, 3) if kcycles else None,
             "device_copy_GBps": round(device_copy_gbps(dev), 1),
-        },
-    }
-    if rank == 0 and world == 1 and not args.no_cpu:
+        }
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         nb = min(nblocks, 1024)
         sample = x[: nb * n].cpu().numpy().view(np.uint16).copy()
         result["cpu_baseline"] = cpu_baseline(sample, nb, n, cfg, args.cpu_seconds)
