@@ -21,6 +21,7 @@ RPP_INVALID_ARGUMENT = -3
 RPP_OUTPUT_TOO_SMALL = -4
 RPP_HIP_ERROR = -5
 RPP_INTERNAL_ERROR = -6
+RPP_CHECKSUM_MISMATCH = -7
 
 RPP_DECODE_AUTO = 0
 RPP_DECODE_FUSED = 1
@@ -37,6 +38,7 @@ STATUS_NAMES = {
     RPP_OUTPUT_TOO_SMALL: "OUTPUT_TOO_SMALL",
     RPP_HIP_ERROR: "HIP_ERROR",
     RPP_INTERNAL_ERROR: "INTERNAL_ERROR",
+    RPP_CHECKSUM_MISMATCH: "CHECKSUM_MISMATCH",
 }
 
 # Every symbol declared in include/ricepp_amd.h.
@@ -74,6 +76,12 @@ EXPORTED_SYMBOLS = (
     "rpp_flac_decode",
     "rpp_flac_decode_batch_workspace_bytes",
     "rpp_flac_decode_batch",
+    "rpp_xxh3_64_batch",
+    "rpp_sha512_256_batch",
+    "rpp_section_headers_batch",
+    "rpp_sections_assemble_batch",
+    "rpp_sections_verify_batch",
+    "rpp_parse_section_header",
 )
 
 
@@ -143,6 +151,21 @@ class RppPcmFormat(C.Structure):
         ("lsb_padded", C.c_uint32),
         ("bytes", C.c_uint32),
         ("bits", C.c_uint32),
+    ]
+
+
+class RppSectionHeader(C.Structure):
+    """``rpp_section_header`` (section_header_v2's fields, include/dwarfs/fstypes.h:85-97)."""
+
+    _fields_ = [
+        ("sha2_512_256", C.c_uint8 * 32),
+        ("xxh3_64", C.c_uint64),
+        ("length", C.c_uint64),
+        ("number", C.c_uint32),
+        ("type", C.c_uint16),
+        ("compression", C.c_uint16),
+        ("major", C.c_uint8),
+        ("minor", C.c_uint8),
     ]
 
 
@@ -230,6 +253,18 @@ def lib() -> C.CDLL:
         L.rpp_flac_decode_batch_workspace_bytes.restype = C.c_uint64
         L.rpp_flac_decode_batch.argtypes = [P, C.c_uint32, P, P, P, P, P, P, P, P, P, P, P, C.c_uint64, P, P]
         L.rpp_flac_decode_batch.restype = C.c_int
+        L.rpp_xxh3_64_batch.argtypes = [P, P, P, C.c_uint32, P, P, P, P]
+        L.rpp_xxh3_64_batch.restype = C.c_int
+        L.rpp_sha512_256_batch.argtypes = [P, P, P, C.c_uint32, P, P, P, P]
+        L.rpp_sha512_256_batch.restype = C.c_int
+        L.rpp_section_headers_batch.argtypes = [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, P, P, P]
+        L.rpp_section_headers_batch.restype = C.c_int
+        L.rpp_sections_assemble_batch.argtypes = [P, P, P, P, P, P, C.c_uint32, P, P, P, P, P]
+        L.rpp_sections_assemble_batch.restype = C.c_int
+        L.rpp_sections_verify_batch.argtypes = [P, C.c_uint64, P, C.c_uint32, C.c_uint32, P, P]
+        L.rpp_sections_verify_batch.restype = C.c_int
+        L.rpp_parse_section_header.argtypes = [P, C.POINTER(RppSectionHeader)]
+        L.rpp_parse_section_header.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

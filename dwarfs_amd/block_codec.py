@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import section as S
 from .codec import CodecConfig, _check, _raise_status, decode_batch, encode_batch
 
 COMPRESSION_TYPE_RICEPP = 7  # include/dwarfs/compression.h
@@ -129,6 +130,35 @@ class RiceppBlockCompressor:
             out.append(hdr + data[o:o + int(sizes[i])].tobytes())
         return out
 
+    def compress_many_sections(self, blocks: Sequence[bytes], metadata: Optional[str], first_number: int = 0) -> bytes:
+        """Compresses many blocks of one category and returns them as image-ready BLOCK sections (header with
+        both checksums + frame + bitstream each, back to back, numbered from ``first_number``): encode,
+        checksums and assembly are one device batch on one stream, and only the finished bytes come back
+        (the writer's fsblock::build_section_header + write, src/writer/filesystem_writer.cpp:606-651)."""
+        cfgs = {self._config(metadata, len(b)) for b in blocks}
+        if not blocks:
+            return b""
+        cfg = cfgs.pop()
+        n = [len(b) // 2 for b in blocks]
+        offs = np.zeros(len(blocks), np.int64)
+        for i in range(1, len(blocks)):
+            offs[i] = offs[i - 1] + (n[i - 1] + 7) // 8 * 8
+        flat = np.zeros(int(offs[-1] + n[-1]) + 8, np.uint16)
+        for o, b in zip(offs, blocks):
+            flat[o:o + len(b) // 2] = np.frombuffer(b, np.uint16)
+        d = torch.from_numpy(flat.view(np.int16)).to(self.device)
+        res = encode_batch(cfg, d, offs, n)
+        frames = [frame_header(len(b), self.block_size, cfg.component_stream_count, 2, cfg.unused_lsb_count,
+                               cfg.byteorder == "big") for b in blocks]
+        d_fr, d_fl = S._rows(frames, S.FRAME_ROW, self.device)
+        headers = S.section_headers_batch(res.data, res.d_offsets, res.sizes, first_number, S.SECTION_TYPE_BLOCK,
+                                          COMPRESSION_TYPE_RICEPP, d_fr, d_fl)
+        capacity = res.data.numel() + len(blocks) * (S.HEADER_BYTES + S.FRAME_ROW)
+        asm = S.sections_assemble_batch(headers, res.data, res.d_offsets, res.sizes, capacity, d_fr, d_fl)
+        torch.cuda.current_stream().synchronize()
+        res.check()
+        return asm.bytes()
+
 
 class RiceppBlockDecompressor:
     """``ricepp_block_decompressor`` (src/compression/ricepp.cpp:184-255)."""
@@ -200,6 +230,59 @@ def decompress_many(decs: Sequence[RiceppBlockDecompressor], device="cuda") -> L
         samples, status = decode_batch(cfg, torch.from_numpy(buf).to(dev), offs, lens, ns)
         torch.cuda.current_stream().synchronize()
         st = status.cpu().numpy()
+        host = samples.cpu().numpy().view(np.uint16)
+        pos = 0
+        for k, i in enumerate(idx):
+            _raise_status(int(st[k]))
+            out[i] = host[pos:pos + ns[k]].tobytes()
+            pos += ns[k]
+    return out  # type: ignore[return-value]
+
+
+def compress_many_sections(blocks: Sequence[bytes], metadata: Optional[str], first_number: int = 0,
+                           block_size: int = 128, device="cuda") -> bytes:
+    """``RiceppBlockCompressor(block_size).compress_many_sections``: image-ready BLOCK sections of one batch."""
+    return RiceppBlockCompressor(block_size, device).compress_many_sections(blocks, metadata, first_number)
+
+
+def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[bytes]:
+    """Decodes the ricepp BLOCK sections of an image fragment (as ``compress_many_sections`` writes them).
+
+    The headers are walked on the host, the image goes to the device in one copy, and the integrity check
+    (``verify`` 1: XXH3-64 as cached_block's check_fast, src/reader/internal/cached_block.cpp:58-67; 2: also
+    SHA-512/256; 0: none) and the decode run on the same stream from that copy.  A section that fails raises
+    ``RuntimeError("block data integrity check failed")`` like the reference, before anything is decoded."""
+    dev = torch.device(device)
+    image = bytes(image)
+    secs, bad_at = S.walk(image)
+    if verify not in (0, 1, 2):
+        raise ValueError("verify must be 0, 1 or 2")
+    if bad_at is not None and not verify:
+        raise RuntimeError(S.INTEGRITY_ERROR)
+    if not secs and bad_at is None:
+        return []
+    padded = np.zeros(len(image) + 64, np.uint8)  # (the decoder reads whole 16-byte granules)
+    padded[:len(image)] = np.frombuffer(image, np.uint8)
+    d_image = torch.from_numpy(padded).to(dev)
+    if verify:
+        offsets = [at for at, _ in secs] + ([bad_at] if bad_at is not None else [])
+        status = S.sections_verify_batch(d_image, len(image), offsets, verify)
+        if int(status.abs().sum().item()) != 0:
+            raise RuntimeError(S.INTEGRITY_ERROR)
+    decs, groups = [], {}
+    for i, (at, h) in enumerate(secs):
+        if h.type != S.SECTION_TYPE_BLOCK or h.compression != COMPRESSION_TYPE_RICEPP:
+            raise RuntimeError(f"section {h.number}: not a ricepp block (type {h.type}, compression {h.compression})")
+        dec =RiceppBlockDecompressor(image[at + S.HEADER_BYTES:at + S.HEADER_BYTES + min(int(h.length), 64)], dev)
+        hdr_len = min(int(h.length), 64) - len(dec.data)
+        decs.append((dec, at + S.HEADER_BYTES + hdr_len, int(h.length) - hdr_len))
+        groups.setdefault(dec.config, []).append(i)
+    out: List[Optional[bytes]] = [None] * len(secs)
+    for cfg, idx in groups.items():
+        ns = [decs[i][0].uncompressed_size() // 2 for i in idx]
+        samples, st = decode_batch(cfg, d_image, [decs[i][1] for i in idx], [decs[i][2] for i in idx], ns)
+        torch.cuda.current_stream().synchronize()
+        st = st.cpu().numpy()
         host = samples.cpu().numpy().view(np.uint16)
         pos = 0
         for k, i in enumerate(idx):

@@ -1300,6 +1300,99 @@ void pcm_sample_transformer::pack(std::span<uint8_t> dst, std::span<int32_t cons
   ctx->sync();
 }
 
+// ---- sections (src/writer/filesystem_writer.cpp:606-651, src/internal/fs_section.cpp:226-259) ----
+//
+// One pooled context per call, no batch queue: the caller already holds a
+// whole batch.  Device buffer layout (all parts 16-aligned): payloads at
+// 16-aligned offsets | u64 offsets, sizes, section sizes, section offsets,
+// total | headers | image.
+
+std::vector<uint8_t> make_sections(std::span<std::span<uint8_t const> const> payloads, uint32_t first_number,
+                                   uint16_t type, uint16_t compression) {
+  const size_t n = payloads.size();
+  if (n == 0) return {};
+  std::vector<uint64_t> tab(2 * n);  // offsets, sizes
+  size_t pay_bytes = 0, image_bytes = 0;
+  for (size_t b = 0; b < n; ++b) {
+    tab[b] = pay_bytes;
+    tab[n + b] = payloads[b].size();
+    pay_bytes += align16(payloads[b].size());
+    image_bytes += 64 + payloads[b].size();
+  }
+  const size_t off_tab = align16(pay_bytes), off_hdr = align16(off_tab + (4 * n + 1) * sizeof(uint64_t)),
+               off_img = off_hdr + 64 * n;
+  const int dev = current_device();
+  ctx_lease ctx{dev};
+  uint8_t* d = ctx->dev(off_img + image_bytes);
+  hipStream_t s = ctx->stream();
+  for (size_t b = 0; b < n; ++b)
+    if (!payloads[b].empty())
+      hip_check(hipMemcpyAsync(d + tab[b], payloads[b].data(), payloads[b].size(), hipMemcpyHostToDevice, s),
+                "H2D section payload");
+  hip_check(hipMemcpyAsync(d + off_tab, tab.data(), 2 * n * sizeof(uint64_t), hipMemcpyHostToDevice, s),
+            "H2D section table");
+  uint64_t* d_tab = reinterpret_cast<uint64_t*>(d + off_tab);
+  int st = rpp_section_headers_batch(d, d_tab, d_tab + n, static_cast<uint32_t>(n), first_number, type, compression,
+                                     nullptr, nullptr, d + off_hdr, s);
+  if (st == RPP_OK)
+    st = rpp_sections_assemble_batch(d + off_hdr, nullptr, nullptr, d, d_tab, d_tab + n, static_cast<uint32_t>(n),
+                                     d + off_img, d_tab + 2 * n, d_tab + 3 * n, d_tab + 4 * n, s);
+  if (st != RPP_OK) {
+    (void)ctx->drain();  // (the copies issued so far read the caller's memory)
+    throw_status(st);
+  }
+  std::vector<uint8_t> image(image_bytes);
+  uint64_t total = 0;
+  hip_check(hipMemcpyAsync(image.data(), d + off_img, image_bytes, hipMemcpyDeviceToHost, s), "D2H sections");
+  hip_check(hipMemcpyAsync(&total, d_tab + 4 * n, sizeof(total), hipMemcpyDeviceToHost, s), "D2H sections total");
+  ctx->sync();
+  if (total != image_bytes) throw std::runtime_error("ricepp_amd: section image length mismatch");
+  return image;
+}
+
+std::vector<uint8_t> make_sections(std::vector<std::vector<uint8_t>> const& payloads, uint32_t first_number,
+                                   uint16_t type, uint16_t compression) {
+  std::vector<std::span<uint8_t const>> spans(payloads.begin(), payloads.end());
+  return make_sections(std::span<std::span<uint8_t const> const>{spans}, first_number, type, compression);
+}
+
+std::vector<int> check_sections(std::span<uint8_t const> image, int level) {
+  if (level < 1 || level > 2) throw std::invalid_argument("check_sections: level must be 1 or 2");
+  // the section walk: each header's length gives the next header's place; a
+  // header that does not parse or runs past the image ends the walk and is
+  // reported by the device's own checks
+  std::vector<uint64_t> offs;
+  for (uint64_t at = 0; at < image.size();) {
+    offs.push_back(at);
+    rpp_section_header h;
+    if (image.size() - at < 64 || rpp_parse_section_header(image.data() + at, &h) != RPP_OK ||
+        h.length > image.size() - at - 64)
+      break;
+    at += 64 + h.length;
+  }
+  const size_t n = offs.size();
+  if (n == 0) return {};
+  const size_t off_tab = align16(image.size()), off_st = off_tab + align16(n * sizeof(uint64_t));
+  const int dev = current_device();
+  ctx_lease ctx{dev};
+  uint8_t* d = ctx->dev(off_st + n * sizeof(int32_t));
+  hipStream_t s = ctx->stream();
+  hip_check(hipMemcpyAsync(d, image.data(), image.size(), hipMemcpyHostToDevice, s), "H2D image");
+  hip_check(hipMemcpyAsync(d + off_tab, offs.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s),
+            "H2D section offsets");
+  const int st = rpp_sections_verify_batch(d, image.size(), reinterpret_cast<uint64_t*>(d + off_tab),
+                                           static_cast<uint32_t>(n), static_cast<uint32_t>(level),
+                                           reinterpret_cast<int32_t*>(d + off_st), s);
+  if (st != RPP_OK) {
+    (void)ctx->drain();
+    throw_status(st);
+  }
+  std::vector<int32_t> status(n);
+  hip_check(hipMemcpyAsync(status.data(), d + off_st, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), "D2H status");
+  ctx->sync();
+  return std::vector<int>(status.begin(), status.end());
+}
+
 // ---- FLAC block codec (src/compression/flac.cpp:215-525) ----
 
 namespace {

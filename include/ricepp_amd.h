@@ -68,6 +68,10 @@ extern "C" {
  * returned for well-formed or malformed input; it reports a bug or a stalled
  * GPU instead of returning wrong samples as RPP_OK. */
 #define RPP_INTERNAL_ERROR (-6)
+/* A section's stored XXH3-64 or SHA-512/256 does not match its bytes
+ * (rpp_sections_verify_batch): the reader's "block data integrity check
+ * failed" (src/reader/internal/cached_block.cpp:58-67). */
+#define RPP_CHECKSUM_MISMATCH (-7)
 
 /* ricepp::codec_config (ricepp/include/ricepp/codec_config.h:36-41). */
 typedef struct rpp_config {
@@ -408,6 +412,94 @@ int rpp_flac_decode_batch(const uint8_t* d_frames, uint32_t nblocks, const uint6
                           const uint32_t* h_max_blocksize, const uint64_t* h_nsamples, int32_t* d_out,
                           const uint64_t* h_out_off, int32_t* d_status, const uint32_t* h_max_candidates,
                           void* d_workspace, uint64_t workspace_bytes, uint32_t* d_ncand, void* stream);
+
+/*
+ * Section checksums and headers (DwarFS section_header_v2,
+ * include/dwarfs/fstypes.h:85-97: "DWARFS", major 2, minor 5, sha2_512_256 at
+ * [8,40), xxh3_64 at [40,48), number [48,52), type [52,54), compression
+ * [54,56), length [56,64), little endian).
+ *
+ *   rpp_section_headers_batch   <- fsblock::build_section_header
+ *   rpp_sections_assemble_batch    (src/writer/filesystem_writer.cpp:606-651), the
+ *                                  writer's two checksums per block, and the
+ *                                  header + data it then writes
+ *   rpp_sections_verify_batch   <- fs_section_v2::check_fast (level 1: XXH3-64,
+ *                                  src/internal/fs_section.cpp:226-259, called by
+ *                                  cached_block, src/reader/internal/cached_block.cpp:58-67)
+ *                                  and fs_section_checker::verify (level 2: also
+ *                                  SHA-512/256, src/internal/fs_section_checker.cpp)
+ *
+ * A message of the two hash calls is an optional prefix followed by a payload
+ * span: message b = d_prefix[64 * b, 64 * b + d_prefix_len[b]) (at most 64
+ * bytes; d_prefix NULL: none) followed by d_data[d_offsets[b], d_offsets[b] +
+ * d_sizes[b]) at any alignment.  XXH3-64 is the 64-bit XXH3 with seed 0 and
+ * the default secret (every length class; messages over 240 bytes take one
+ * wave each, shorter ones one lane each); SHA-512/256 is FIPS 180-4 (one lane
+ * per message, below 2^61 bytes).  d_hash[b] receives the XXH3 value,
+ * d_digest[32 * b ..] the 32 digest bytes.  Like every *_batch call: device
+ * pointers, asynchronous on `stream`, n == 0 returns RPP_OK at once.
+ */
+int rpp_xxh3_64_batch(const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes, uint32_t n,
+                      const uint8_t* d_prefix, const uint32_t* d_prefix_len, uint64_t* d_hash, void* stream);
+int rpp_sha512_256_batch(const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes, uint32_t n,
+                         const uint8_t* d_prefix, const uint32_t* d_prefix_len, uint8_t* d_digest, void* stream);
+
+/*
+ * Complete v2 headers of n sections of one type: section b holds
+ * d_frame[32 * b, 32 * b + d_frame_len[b]) (the DwarFS frame header of a
+ * ricepp block, rpp_frame_header; d_frame NULL: none) followed by
+ * d_payload[d_payload_offsets[b], + d_payload_sizes[b]).  d_headers[64 * b ..]
+ * receives magic, version 2.5, number = first_number + b, type, compression
+ * (both < 2^16), length = frame length + payload size, the XXH3-64 over
+ * header[48,64) + data and then the SHA-512/256 over header[40,64) + data,
+ * in the reference's order.
+ */
+int rpp_section_headers_batch(const uint8_t* d_payload, const uint64_t* d_payload_offsets,
+                              const uint64_t* d_payload_sizes, uint32_t n, uint32_t first_number,
+                              uint32_t section_type, uint32_t compression, const uint8_t* d_frame,
+                              const uint32_t* d_frame_len, uint8_t* d_headers, void* stream);
+
+/*
+ * Image fragment of n sections, byte-packed as the writer appends them:
+ * header b, frame b, payload b back to back at d_image + d_section_offsets[b],
+ * section b + 1 right behind (no alignment on either side, unlike
+ * rpp_pack_batch).  Written: d_section_sizes[b] = 64 + frame length + payload
+ * size, d_section_offsets[b] = their exclusive sum (rpp_exclusive_scan_u64),
+ * *d_total = the fragment's length (d_total may be NULL).  d_image must hold
+ * the sum of the sections' sizes.
+ */
+int rpp_sections_assemble_batch(const uint8_t* d_headers, const uint8_t* d_frame, const uint32_t* d_frame_len,
+                                const uint8_t* d_payload, const uint64_t* d_payload_offsets,
+                                const uint64_t* d_payload_sizes, uint32_t n, uint8_t* d_image,
+                                uint64_t* d_section_sizes, uint64_t* d_section_offsets, uint64_t* d_total,
+                                void* stream);
+
+/*
+ * Integrity check of the n sections whose headers start at
+ * d_image + d_section_offsets[b], in an image of image_bytes bytes.  level 1
+ * checks the XXH3-64, level 2 the SHA-512/256 as well.  d_status[b]: RPP_OK;
+ * RPP_CHECKSUM_MISMATCH; RPP_INVALID_ARGUMENT for a header without the magic
+ * or with another major version; RPP_TRUNCATED_INPUT when the header or its
+ * length runs past image_bytes (nothing beyond image_bytes is read).
+ */
+int rpp_sections_verify_batch(const uint8_t* d_image, uint64_t image_bytes, const uint64_t* d_section_offsets,
+                              uint32_t n, uint32_t level, int32_t* d_status, void* stream);
+
+/* section_header_v2's fields (host memory). */
+typedef struct rpp_section_header {
+  uint8_t sha2_512_256[32];
+  uint64_t xxh3_64;
+  uint64_t length;
+  uint32_t number;
+  uint16_t type;
+  uint16_t compression;
+  uint8_t major;
+  uint8_t minor;
+} rpp_section_header;
+
+/* Parses a 64-byte section header: RPP_OK, or RPP_INVALID_ARGUMENT for a
+ * wrong magic or major version (nothing is written then). */
+int rpp_parse_section_header(const uint8_t in[64], rpp_section_header* out);
 
 #ifdef __cplusplus
 }

@@ -238,6 +238,27 @@ class pcm_sample_transformer {
   int device_ = 0;
 };
 
+// ---- sections (include/dwarfs/fstypes.h:85-97) ----
+//
+// make_sections: the image bytes of one section per payload, numbered from
+// first_number -- each a section_header_v2 with both checksums
+// (fsblock::build_section_header, src/writer/filesystem_writer.cpp:606-651)
+// followed by its payload, back to back as the writer appends them.  The
+// headers are computed and the image assembled on the GPU
+// (rpp_section_headers_batch, rpp_sections_assemble_batch).
+// check_sections: walks the sections of `image` from offset 0 and checks
+// them on the GPU (rpp_sections_verify_batch): level 1 is
+// fs_section::check_fast (XXH3-64, src/internal/fs_section.cpp:226-259),
+// level 2 also fs_section_checker::verify's SHA-512/256.  One RPP_* status per
+// section found; a header that does not parse or runs past the image is the
+// last one reported.  Both take a pooled device context on the current device;
+// the batch queue is not involved.
+std::vector<uint8_t> make_sections(std::span<std::span<uint8_t const> const> payloads, uint32_t first_number,
+                                   uint16_t type, uint16_t compression);
+std::vector<uint8_t> make_sections(std::vector<std::vector<uint8_t>> const& payloads, uint32_t first_number,
+                                   uint16_t type, uint16_t compression);
+std::vector<int> check_sections(std::span<uint8_t const> image, int level);
+
 // ---- facade statistics (tests and benchmarks) ----
 struct facade_stats {
   uint64_t encode_launches, encode_blocks, decode_launches, decode_blocks;
