@@ -82,7 +82,20 @@ EXPORTED_SYMBOLS = (
     "rpp_sections_assemble_batch",
     "rpp_sections_verify_batch",
     "rpp_parse_section_header",
+    "rpp_file_hash_algo",
+    "rpp_file_hash_digest_bytes",
+    "rpp_xxh3_128_batch",
+    "rpp_file_hash_batch",
+    "rpp_group_workspace_bytes",
+    "rpp_group_first_batch",
+    "rpp_group_start_slot",
+    "rpp_file_dedup_workspace_bytes",
+    "rpp_file_dedup_batch",
 )
+
+RPP_HASH_XXH3_64 = 0
+RPP_HASH_XXH3_128 = 1
+RPP_HASH_SHA512_256 = 2
 
 
 class RppConfig(C.Structure):
@@ -265,6 +278,24 @@ def lib() -> C.CDLL:
         L.rpp_sections_verify_batch.restype = C.c_int
         L.rpp_parse_section_header.argtypes = [P, C.POINTER(RppSectionHeader)]
         L.rpp_parse_section_header.restype = C.c_int
+        L.rpp_file_hash_algo.argtypes = [C.c_char_p]
+        L.rpp_file_hash_algo.restype = C.c_int
+        L.rpp_file_hash_digest_bytes.argtypes = [C.c_int]
+        L.rpp_file_hash_digest_bytes.restype = C.c_int
+        L.rpp_xxh3_128_batch.argtypes = [P, P, P, C.c_uint32, P, P, P, P]
+        L.rpp_xxh3_128_batch.restype = C.c_int
+        L.rpp_file_hash_batch.argtypes = [C.c_int, P, P, P, P, C.c_uint32, P, P]
+        L.rpp_file_hash_batch.restype = C.c_int
+        L.rpp_group_workspace_bytes.argtypes = [C.c_uint32]
+        L.rpp_group_workspace_bytes.restype = C.c_uint64
+        L.rpp_group_first_batch.argtypes = [P, P, C.c_uint32, P, C.c_uint32, P, P, P, C.c_uint64, P]
+        L.rpp_group_first_batch.restype = C.c_int
+        L.rpp_group_start_slot.argtypes = [C.c_uint64, P, C.c_uint32, C.c_uint32]
+        L.rpp_group_start_slot.restype = C.c_uint64
+        L.rpp_file_dedup_workspace_bytes.argtypes = [C.c_uint32]
+        L.rpp_file_dedup_workspace_bytes.restype = C.c_uint64
+        L.rpp_file_dedup_batch.argtypes = [C.c_int, P, P, P, C.c_uint32, P, P, P, P, C.c_uint64, P]
+        L.rpp_file_dedup_batch.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

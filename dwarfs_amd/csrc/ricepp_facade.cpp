@@ -1393,6 +1393,61 @@ std::vector<int> check_sections(std::span<uint8_t const> image, int level) {
   return std::vector<int>(status.begin(), status.end());
 }
 
+// ---- duplicate files (src/writer/internal/file_scanner.cpp:274-413) ----
+//
+// Device buffer layout (all parts 16-aligned): files at 16-aligned offsets |
+// u64 offsets, sizes | digests | first | hashed | workspace.
+
+duplicate_files find_duplicates(std::span<std::span<uint8_t const> const> files, std::string_view algo) {
+  const std::string name{algo};
+  const int a = rpp_file_hash_algo(name.c_str());
+  if (a < 0) throw std::runtime_error("ricepp_amd: unknown file hash algorithm: " + name);
+  duplicate_files res;
+  res.digest_size = static_cast<size_t>(rpp_file_hash_digest_bytes(a));
+  const size_t n = files.size();
+  if (n == 0) return res;
+  if (n > (size_t{1} << 30)) throw std::invalid_argument("find_duplicates: too many files");
+  std::vector<uint64_t> tab(2 * n);  // offsets, sizes
+  size_t file_bytes = 0;
+  for (size_t b = 0; b < n; ++b) {
+    tab[b] = file_bytes;
+    tab[n + b] = files[b].size();
+    file_bytes += align16(files[b].size());
+  }
+  const uint64_t ws_bytes = rpp_file_dedup_workspace_bytes(static_cast<uint32_t>(n));
+  const size_t off_tab = align16(file_bytes), off_dig = align16(off_tab + 2 * n * sizeof(uint64_t)),
+               off_first = align16(off_dig + n * res.digest_size), off_hashed = align16(off_first + n * sizeof(uint32_t)),
+               off_ws = align16(off_hashed + n);
+  const int dev = current_device();
+  ctx_lease ctx{dev};
+  uint8_t* d = ctx->dev(off_ws + ws_bytes);
+  hipStream_t s = ctx->stream();
+  for (size_t b = 0; b < n; ++b)
+    if (!files[b].empty())
+      hip_check(hipMemcpyAsync(d + tab[b], files[b].data(), files[b].size(), hipMemcpyHostToDevice, s), "H2D file");
+  hip_check(hipMemcpyAsync(d + off_tab, tab.data(), 2 * n * sizeof(uint64_t), hipMemcpyHostToDevice, s),
+            "H2D file table");
+  hip_check(hipMemsetAsync(d + off_dig, 0, n * res.digest_size, s), "clear digests");
+  uint64_t* d_tab = reinterpret_cast<uint64_t*>(d + off_tab);
+  const int st = rpp_file_dedup_batch(a, d, d_tab, d_tab + n, static_cast<uint32_t>(n), d + off_dig,
+                                      reinterpret_cast<uint32_t*>(d + off_first), d + off_hashed, d + off_ws, ws_bytes,
+                                      s);
+  if (st != RPP_OK) {
+    (void)ctx->drain();  // (the copies issued so far read the caller's memory)
+    throw_status(st);
+  }
+  res.first.resize(n);
+  res.hashed.resize(n);
+  res.digests.resize(n * res.digest_size);
+  hip_check(hipMemcpyAsync(res.first.data(), d + off_first, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s),
+            "D2H first");
+  hip_check(hipMemcpyAsync(res.hashed.data(), d + off_hashed, n, hipMemcpyDeviceToHost, s), "D2H hashed");
+  hip_check(hipMemcpyAsync(res.digests.data(), d + off_dig, res.digests.size(), hipMemcpyDeviceToHost, s),
+            "D2H digests");
+  ctx->sync();
+  return res;
+}
+
 // ---- FLAC block codec (src/compression/flac.cpp:215-525) ----
 
 namespace {

@@ -30,6 +30,12 @@
 //   is small (message i -> wave i % W, lane i / W), so few messages run on many
 //   SIMDs instead of in the lanes of one.
 //
+// The same kernels hash files for the scanner's duplicate detection
+// (file_scanner_::scan_dedupe, src/writer/internal/file_scanner.cpp:274-413;
+// the rpp_file_hash_batch ... rpp_file_dedup_batch group): XXH3-128 shares the
+// long loop and has short formulas of its own, a select mask skips messages,
+// and two small kernels group equal (size, digest) keys in a hash table.
+//
 // Every shift and rotate has a compile-time constant amount.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -119,6 +125,10 @@ struct Job {
   uint32_t out_stride;
   uint32_t sections, from;
   int32_t* status;
+  // file hashing: message b is skipped (not read, nothing written) where select[b] == 0 or its size is below
+  // min_size; a nonzero clamp hashes the first min(size, clamp) bytes only
+  const uint8_t* select;
+  uint64_t min_size, clamp;
 };
 
 struct Msg {
@@ -147,6 +157,7 @@ __device__ __forceinline__ u64pair ld128(const uint8_t* p) {
 }
 
 __device__ __forceinline__ bool load_msg(const Job& j, uint32_t b, Msg& m) {
+  if (j.select && !j.select[b]) return false;
   if (j.sections) {
     if (j.status[b] != RPP_OK) return false;
     const uint8_t* h = j.data + j.offs[b];
@@ -169,8 +180,11 @@ __device__ __forceinline__ bool load_msg(const Job& j, uint32_t b, Msg& m) {
   m.p1 = j.seg1 + (size_t)kFrameRow * b;
   m.l0 = l0;
   m.pre = l0 + l1;
+  uint64_t size = j.sizes[b];
+  if (size < j.min_size) return false;
+  if (j.clamp && size > j.clamp) size = j.clamp;
   m.pay = j.data + j.offs[b];
-  m.len = (uint64_t)m.pre + j.sizes[b];
+  m.len = (uint64_t)m.pre + size;
   return true;
 }
 
@@ -293,6 +307,80 @@ __global__ __launch_bounds__(64) void rpp_xxh3_short_kernel(Job job, uint32_t n,
   emit_xxh(job, b, xxh3_short(m));
 }
 
+// ---- XXH3-128, seed 0, default secret: {low64, high64} ----
+
+__device__ __forceinline__ u64pair mix32(u64pair acc, const Msg& m, uint64_t p1, uint64_t p2, uint32_t s) {
+  const u64pair d1 = msg_r128(m, p1), d2 = msg_r128(m, p2);
+  acc.a += fold64(d1.a ^ sec64(s), d1.b ^ sec64(s + 8));
+  acc.a ^= d2.a + d2.b;
+  acc.b += fold64(d2.a ^ sec64(s + 16), d2.b ^ sec64(s + 24));
+  acc.b ^= d1.a + d1.b;
+  return acc;
+}
+
+// len <= 240
+__device__ u64pair xxh3_128_short(const Msg& m) {
+  const uint64_t len = m.len;
+  if (len == 0) return u64pair{aval64(sec64(64) ^ sec64(72)), aval64(sec64(80) ^ sec64(88))};
+  if (len <= 3) {
+    const uint32_t c1 = msg_byte(m, 0), c2 = msg_byte(m, len >> 1), c3 = msg_byte(m, len - 1);
+    const uint32_t lo = (c1 << 16) | (c2 << 24) | c3 | ((uint32_t)len << 8);
+    const uint32_t sw = __builtin_bswap32(lo), hi = (sw << 13) | (sw >> 19);
+    return u64pair{aval64((uint64_t)(lo ^ sec32(0) ^ sec32(4))), aval64((uint64_t)(hi ^ sec32(8) ^ sec32(12)))};
+  }
+  if (len <= 8) {
+    const uint64_t in_lo = msg_r32(m, 0), in_hi = msg_r32(m, len - 4);
+    const uint64_t keyed = (in_lo + (in_hi << 32)) ^ (sec64(16) ^ sec64(24));
+    const uint64_t mul = P64_1 + (len << 2);
+    uint64_t lo = keyed * mul, hi = __umul64hi(keyed, mul);
+    hi += lo << 1;
+    lo ^= hi >> 3;
+    lo ^= lo >> 35;
+    lo *= MX2;
+    lo ^= lo >> 28;
+    return u64pair{lo, aval(hi)};
+  }
+  if (len <= 16) {
+    const uint64_t in_lo = msg_r64(m, 0);
+    uint64_t in_hi = msg_r64(m, len - 8);
+    const uint64_t x = in_lo ^ in_hi ^ (sec64(32) ^ sec64(40));
+    uint64_t mlo = x * P64_1, mhi = __umul64hi(x, P64_1);
+    mlo += (len - 1) << 54;
+    in_hi ^= sec64(48) ^ sec64(56);
+    mhi += in_hi + (in_hi & 0xFFFFFFFFull) * (P32_2 - 1);
+    mlo ^= __builtin_bswap64(mhi);
+    return u64pair{aval(mlo * P64_2), aval(__umul64hi(mlo, P64_2) + mhi * P64_2)};
+  }
+  u64pair acc{len * P64_1, 0};
+  if (len <= 128) {
+    // (the pairs from the middle outwards: unlike the 64-bit sum, the order matters)
+    for (uint32_t i = (uint32_t)((len - 1) >> 5) + 1; i-- > 0;) acc = mix32(acc, m, 16 * i, len - 16 * (i + 1), 32 * i);
+  } else {
+    for (uint32_t i = 0; i < 4; ++i) acc = mix32(acc, m, 32 * i, 32 * i + 16, 32 * i);
+    acc.a = aval(acc.a);
+    acc.b = aval(acc.b);
+    const uint32_t rounds = (uint32_t)(len >> 5);
+    for (uint32_t i = 4; i < rounds; ++i) acc = mix32(acc, m, 32 * i, 32 * i + 16, 3 + 32 * (i - 4));
+    acc = mix32(acc, m, len - 16, len - 32, 103);
+  }
+  return u64pair{aval(acc.a + acc.b), 0 - aval(acc.a * P64_1 + acc.b * P64_4 + len * P64_2)};
+}
+
+// DwarFS's digest order (checksum_xxh3::finalize, src/checksum.cpp:185-196):
+// the low 64 bits little endian, then the high 64
+__device__ __forceinline__ void emit_xxh128(const Job& j, uint32_t b, u64pair h) {
+  __builtin_memcpy(j.out + (size_t)j.out_stride * b, &h, 16);
+}
+
+__global__ __launch_bounds__(64) void rpp_xxh3_128_short_kernel(Job job, uint32_t n, uint32_t nwaves) {
+  const uint64_t id = lane_message(nwaves);
+  if (id >= n) return;
+  const uint32_t b = (uint32_t)id;
+  Msg m;
+  if (!load_msg(job, b, m) || m.len > 240) return;
+  emit_xxh128(job, b, xxh3_128_short(m));
+}
+
 // sum over the 16 lanes that share lane % 4
 __device__ __forceinline__ uint64_t stripe_sum(uint64_t v) {
   v += __shfl_xor(v, 4, 64);
@@ -302,8 +390,11 @@ __device__ __forceinline__ uint64_t stripe_sum(uint64_t v) {
   return v;
 }
 
-// len > 240: one wave per message
-__global__ __launch_bounds__(64 * kLongWaves) void rpp_xxh3_long_kernel(Job job, uint32_t n) {
+// len > 240: one wave per message.  The 128-bit value (Wide) runs the same
+// loop; its low half is the 64-bit merge, its high half a second merge over
+// the secret's tail (offset 192 - 64 - 11) started from ~(len * PRIME64_2).
+template <bool Wide>
+__device__ __forceinline__ void xxh3_long(const Job& job, uint32_t n) {
   const uint32_t lane = threadIdx.x % 64, b = blockIdx.x * kLongWaves + threadIdx.x / 64;
   if (b >= n) return;  // (wave-uniform, like every exit below)
   Msg m;
@@ -349,7 +440,21 @@ __global__ __launch_bounds__(64 * kLongWaves) void rpp_xxh3_long_kernel(Job job,
   uint64_t f = fold64(a0 ^ sec64(11 + 16 * q), a1 ^ sec64(19 + 16 * q));
   f += __shfl_xor(f, 1, 64);
   f += __shfl_xor(f, 2, 64);
-  if (lane == 0) emit_xxh(job, b, aval(len * P64_1 + f));
+  if constexpr (Wide) {
+    uint64_t g = fold64(a0 ^ sec64(117 + 16 * q), a1 ^ sec64(125 + 16 * q));
+    g += __shfl_xor(g, 1, 64);
+    g += __shfl_xor(g, 2, 64);
+    if (lane == 0) emit_xxh128(job, b, u64pair{aval(len * P64_1 + f), aval(~(len * P64_2) + g)});
+  } else {
+    if (lane == 0) emit_xxh(job, b, aval(len * P64_1 + f));
+  }
+}
+
+__global__ __launch_bounds__(64 * kLongWaves) void rpp_xxh3_long_kernel(Job job, uint32_t n) {
+  xxh3_long<false>(job, n);
+}
+__global__ __launch_bounds__(64 * kLongWaves) void rpp_xxh3_128_long_kernel(Job job, uint32_t n) {
+  xxh3_long<true>(job, n);
 }
 
 // ---- SHA-512/256 ----
@@ -548,7 +653,119 @@ __global__ __launch_bounds__(kCopyThreads) void rpp_section_copy_kernel(
   if (total && b == n - 1 && t == 0) *total = section_offs[b] + kHeaderBytes + fl + psize;
 }
 
+// ---- grouping equal keys (file_scanner_::scan_dedupe's unique_size_ / by_hash_ maps) ----
+//
+// A key is sizes[b] plus `words` 64-bit words of digest row b.  Open addressing
+// over `mask + 1` >= 2n slots of key indices, linear probing from key_slot().
+// A slot's occupant only ever changes to a smaller index with the same key and
+// a slot never empties, so a key's probe sequence always ends at the same slot:
+// all equal keys settle in one slot, which ends up holding their smallest index
+// whatever the order the lanes ran in.
+
+constexpr uint32_t kEmptySlot = 0xFFFFFFFFu;
+constexpr uint32_t kGroupThreads = 256;
+
+struct Keys {
+  const uint64_t* sizes;
+  const uint8_t* digest;  // rows of 8 * words bytes
+  uint32_t words;
+  const uint8_t* select;
+};
+
+__host__ __device__ inline uint64_t key_mix(uint64_t h, uint64_t w) {
+  h = (h ^ w) * P64_2;
+  return h ^ (h >> 29);
+}
+// start slot of a key, before masking
+__host__ __device__ inline uint64_t key_finish(uint64_t h) {
+  h *= P64_3;
+  return h ^ (h >> 32);
+}
+
+__device__ __forceinline__ uint64_t key_slot(const Keys& k, uint32_t b) {
+  uint64_t h = key_mix(P64_1, k.sizes[b]);
+  for (uint32_t w = 0; w < k.words; ++w) h = key_mix(h, ld64(k.digest + 8 * ((size_t)k.words * b + w)));
+  return key_finish(h);
+}
+__device__ __forceinline__ bool key_equal(const Keys& k, uint32_t a, uint32_t b) {
+  bool same = k.sizes[a] == k.sizes[b];
+  for (uint32_t w = 0; w < k.words; ++w)
+    same = same && ld64(k.digest + 8 * ((size_t)k.words * a + w)) == ld64(k.digest + 8 * ((size_t)k.words * b + w));
+  return same;
+}
+
+__global__ __launch_bounds__(kGroupThreads) void rpp_group_insert_kernel(Keys k, uint32_t n, uint32_t* table,
+                                                                          uint32_t mask) {
+  const uint32_t b = blockIdx.x * kGroupThreads + threadIdx.x;
+  if (b >= n || (k.select && !k.select[b])) return;
+  uint32_t slot = (uint32_t)key_slot(k, b) & mask;
+  // (at most n slots are ever occupied, of more than n: the walk meets an empty one)
+  for (uint32_t probes = 0; probes <= mask; ++probes) {
+    const uint32_t cur = atomicCAS(table + slot, kEmptySlot, b);
+    if (cur == kEmptySlot) return;
+    if (cur < n && key_equal(k, cur, b)) {
+      atomicMin(table + slot, b);
+      return;
+    }
+    slot = (slot + 1) & mask;
+  }
+}
+
+// (a launch of its own: every insert is done)
+__global__ __launch_bounds__(kGroupThreads) void rpp_group_lookup_kernel(Keys k, uint32_t n, const uint32_t* table,
+                                                                          uint32_t mask, uint32_t* first,
+                                                                          uint8_t* multi) {
+  const uint32_t b = blockIdx.x * kGroupThreads + threadIdx.x;
+  if (b >= n) return;
+  uint32_t f = b;
+  if (!k.select || k.select[b]) {
+    uint32_t slot = (uint32_t)key_slot(k, b) & mask;
+    for (uint32_t probes = 0; probes <= mask; ++probes) {
+      const uint32_t cur = table[slot];
+      if (cur >= n) break;  // (empty: cannot happen after the insert)
+      if (key_equal(k, cur, b)) {
+        f = cur;
+        break;
+      }
+      slot = (slot + 1) & mask;
+    }
+  }
+  first[b] = f;
+  if (f != b && multi) {
+    multi[b] = 1;
+    multi[f] = 1;
+  }
+}
+
+// slots of the table for n keys: the power of two >= 2n (and >= 4)
+uint64_t group_slots(uint32_t n) {
+  uint64_t s = 4;
+  while (s < 2ull * n) s <<= 1;
+  return s;
+}
+
 int launched() { return hipGetLastError() == hipSuccess ? RPP_OK : RPP_HIP_ERROR; }
+
+int launch_group(const Keys& k, uint32_t n, uint32_t* first, uint8_t* multi, void* ws, hipStream_t s) {
+  const uint64_t slots = group_slots(n);
+  uint32_t* table = static_cast<uint32_t*>(ws);
+  if (hipMemsetAsync(table, 0xFF, slots * sizeof(uint32_t), s) != hipSuccess) return RPP_HIP_ERROR;
+  if (multi && hipMemsetAsync(multi, 0, n, s) != hipSuccess) return RPP_HIP_ERROR;
+  const uint32_t grid = (n + kGroupThreads - 1) / kGroupThreads, mask = (uint32_t)(slots - 1);
+  hipLaunchKernelGGL(rpp_group_insert_kernel, dim3(grid), dim3(kGroupThreads), 0, s, k, n, table, mask);
+  if (launched() != RPP_OK) return RPP_HIP_ERROR;
+  hipLaunchKernelGGL(rpp_group_lookup_kernel, dim3(grid), dim3(kGroupThreads), 0, s, k, n, table, mask, first, multi);
+  return launched();
+}
+
+int launch_xxh3_128(const Job& job, uint32_t n, hipStream_t s) {
+  const uint32_t nw = lane_waves(n);
+  hipLaunchKernelGGL(rpp_xxh3_128_short_kernel, dim3(nw), dim3(64), 0, s, job, n, nw);
+  if (launched() != RPP_OK) return RPP_HIP_ERROR;
+  hipLaunchKernelGGL(rpp_xxh3_128_long_kernel, dim3((n + kLongWaves - 1) / kLongWaves), dim3(64 * kLongWaves), 0, s,
+                     job, n);
+  return launched();
+}
 
 int launch_xxh3(const Job& job, uint32_t n, hipStream_t s) {
   const uint32_t nw = lane_waves(n);
@@ -596,6 +813,122 @@ extern "C" int rpp_sha512_256_batch(const uint8_t* d_data, const uint64_t* d_off
   if (!d_data || !d_offsets || !d_sizes || !d_digest || (d_prefix && !d_prefix_len)) return RPP_INVALID_ARGUMENT;
   return launch_sha(plain_job(d_data, d_offsets, d_sizes, d_prefix, d_prefix_len, d_digest, 32), n,
                     (hipStream_t)stream);
+}
+
+extern "C" int rpp_xxh3_128_batch(const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                                  uint32_t n, const uint8_t* d_prefix, const uint32_t* d_prefix_len,
+                                  uint8_t* d_digest, void* stream) {
+  if (n == 0) return RPP_OK;
+  if (!d_data || !d_offsets || !d_sizes || !d_digest || (d_prefix && !d_prefix_len)) return RPP_INVALID_ARGUMENT;
+  return launch_xxh3_128(plain_job(d_data, d_offsets, d_sizes, d_prefix, d_prefix_len, d_digest, 16), n,
+                         (hipStream_t)stream);
+}
+
+// ---- duplicate-file detection (file_scanner_::scan_dedupe, src/writer/internal/file_scanner.cpp:274-413) ----
+
+namespace {
+
+constexpr uint64_t kLargeFileThreshold = 1024 * 1024;  // file_scanner.cpp:59
+constexpr uint64_t kLargeFileStartHashSize = 4096;     // file_scanner.cpp:60
+constexpr uint32_t kGroupMaxKeys = 1u << 30;
+
+int launch_file_hash(int algo, Job job, uint32_t n, hipStream_t s) {
+  job.out_stride = (uint32_t)rpp_file_hash_digest_bytes(algo);
+  switch (algo) {
+    case RPP_HASH_XXH3_64: return launch_xxh3(job, n, s);
+    case RPP_HASH_XXH3_128: return launch_xxh3_128(job, n, s);
+    case RPP_HASH_SHA512_256: return launch_sha(job, n, s);
+  }
+  return RPP_INVALID_ARGUMENT;
+}
+
+uint64_t align16u(uint64_t v) { return (v + 15) & ~15ull; }
+
+}  // namespace
+
+extern "C" int rpp_file_hash_algo(const char* name) {
+  if (!name) return -1;
+  if (!strcmp(name, "xxh3-64")) return RPP_HASH_XXH3_64;
+  if (!strcmp(name, "xxh3-128")) return RPP_HASH_XXH3_128;
+  if (!strcmp(name, "sha512-256")) return RPP_HASH_SHA512_256;
+  return -1;
+}
+
+extern "C" int rpp_file_hash_digest_bytes(int algo) {
+  switch (algo) {
+    case RPP_HASH_XXH3_64: return 8;
+    case RPP_HASH_XXH3_128: return 16;
+    case RPP_HASH_SHA512_256: return 32;
+  }
+  return 0;
+}
+
+extern "C" int rpp_file_hash_batch(int algo, const uint8_t* d_data, const uint64_t* d_offsets,
+                                   const uint64_t* d_sizes, const uint8_t* d_select, uint32_t n, uint8_t* d_digest,
+                                   void* stream) {
+  if (rpp_file_hash_digest_bytes(algo) == 0) return RPP_INVALID_ARGUMENT;
+  if (n == 0) return RPP_OK;
+  if (!d_data || !d_offsets || !d_sizes || !d_digest) return RPP_INVALID_ARGUMENT;
+  Job j = plain_job(d_data, d_offsets, d_sizes, nullptr, nullptr, d_digest, 0);
+  j.select = d_select;
+  return launch_file_hash(algo, j, n, (hipStream_t)stream);
+}
+
+extern "C" uint64_t rpp_group_workspace_bytes(uint32_t n) { return group_slots(n) * sizeof(uint32_t); }
+
+extern "C" uint64_t rpp_group_start_slot(uint64_t size, const uint8_t* digest, uint32_t digest_bytes, uint32_t n) {
+  uint64_t h = key_mix(P64_1, size);
+  for (uint32_t w = 0; digest && w < digest_bytes / 8; ++w) {
+    uint64_t v;
+    memcpy(&v, digest + 8 * w, 8);
+    h = key_mix(h, v);
+  }
+  return key_finish(h) & 0xFFFFFFFFu & (group_slots(n) - 1);
+}
+
+extern "C" int rpp_group_first_batch(const uint64_t* d_sizes, const uint8_t* d_digest, uint32_t digest_bytes,
+                                     const uint8_t* d_select, uint32_t n, uint32_t* d_first, uint8_t* d_multi,
+                                     void* d_workspace, uint64_t workspace_bytes, void* stream) {
+  if (digest_bytes != 0 && digest_bytes != 8 && digest_bytes != 16 && digest_bytes != 32) return RPP_INVALID_ARGUMENT;
+  if (n == 0) return RPP_OK;
+  if (!d_sizes || !d_first || !d_workspace || n > kGroupMaxKeys || workspace_bytes < rpp_group_workspace_bytes(n))
+    return RPP_INVALID_ARGUMENT;
+  const Keys k{d_sizes, d_digest, d_digest ? digest_bytes / 8 : 0u, d_select};
+  return launch_group(k, n, d_first, d_multi, d_workspace, (hipStream_t)stream);
+}
+
+// workspace: the table | one start hash per file
+extern "C" uint64_t rpp_file_dedup_workspace_bytes(uint32_t n) {
+  return align16u(rpp_group_workspace_bytes(n)) + sizeof(uint64_t) * (uint64_t)n;
+}
+
+extern "C" int rpp_file_dedup_batch(int algo, const uint8_t* d_data, const uint64_t* d_offsets,
+                                    const uint64_t* d_sizes, uint32_t n, uint8_t* d_digest, uint32_t* d_first,
+                                    uint8_t* d_hashed, void* d_workspace, uint64_t workspace_bytes, void* stream) {
+  const uint32_t dbytes = (uint32_t)rpp_file_hash_digest_bytes(algo);
+  if (dbytes == 0) return RPP_INVALID_ARGUMENT;
+  if (n == 0) return RPP_OK;
+  if (!d_data || !d_offsets || !d_sizes || !d_digest || !d_first || !d_hashed || !d_workspace || n > kGroupMaxKeys ||
+      workspace_bytes < rpp_file_dedup_workspace_bytes(n))
+    return RPP_INVALID_ARGUMENT;
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t* d_start = static_cast<uint8_t*>(d_workspace) + align16u(rpp_group_workspace_bytes(n));
+  // the scanner's start hash: XXH3-64 of the first 4 KiB of a file of 1 MiB and up, 0 below
+  if (hipMemsetAsync(d_start, 0, sizeof(uint64_t) * (size_t)n, s) != hipSuccess) return RPP_HIP_ERROR;
+  Job j = plain_job(d_data, d_offsets, d_sizes, nullptr, nullptr, d_start, 8);
+  j.min_size = kLargeFileThreshold;
+  j.clamp = kLargeFileStartHashSize;
+  int st = launch_xxh3(j, n, s);
+  if (st != RPP_OK) return st;
+  // files sharing (size, start hash) are hashed (d_first is scratch here) ...
+  st = launch_group(Keys{d_sizes, d_start, 1, nullptr}, n, d_first, d_hashed, d_workspace, s);
+  if (st != RPP_OK) return st;
+  j = plain_job(d_data, d_offsets, d_sizes, nullptr, nullptr, d_digest, 0);
+  j.select = d_hashed;
+  st = launch_file_hash(algo, j, n, s);
+  if (st != RPP_OK) return st;
+  // ... and those with equal (size, digest) share the first one's inode
+  return launch_group(Keys{d_sizes, d_digest, dbytes / 8, d_hashed}, n, d_first, nullptr, d_workspace, s);
 }
 
 extern "C" int rpp_section_headers_batch(const uint8_t* d_payload, const uint64_t* d_payload_offsets,

@@ -80,6 +80,20 @@ def xxh3_64_batch(data: torch.Tensor, offsets, sizes, prefix=None, prefix_len=No
     return out
 
 
+def xxh3_128_batch(data: torch.Tensor, offsets, sizes, prefix=None, prefix_len=None,
+                   stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """XXH3-128 (seed 0) of the same messages as :func:`xxh3_64_batch`: a uint8 device tensor [n, 16] in
+    DwarFS's digest order (low64 little endian, then high64 little endian)."""
+    dev = data.device
+    d_off, d_sz = _i64(offsets, dev), _i64(sizes, dev)
+    n = d_sz.numel()
+    d_pre, d_plen = _prefix_args(prefix, prefix_len, dev)
+    out = torch.empty((n, 16), dtype=torch.uint8, device=dev)
+    _raise_status(N.lib().rpp_xxh3_128_batch(_ptr(data), _ptr(d_off), _ptr(d_sz), n, _ptr(d_pre), _ptr(d_plen),
+                                             _ptr(out), _stream_ptr(stream)))
+    return out
+
+
 def sha512_256_batch(data: torch.Tensor, offsets, sizes, prefix=None, prefix_len=None,
                      stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """SHA-512/256 of the same messages as :func:`xxh3_64_batch`: a uint8 device tensor [n, 32]."""

@@ -501,6 +501,81 @@ typedef struct rpp_section_header {
  * wrong magic or major version (nothing is written then). */
 int rpp_parse_section_header(const uint8_t in[64], rpp_section_header* out);
 
+/*
+ * Duplicate-file detection (file_scanner_::scan_dedupe and hash_file,
+ * src/writer/internal/file_scanner.cpp:274-413; the algorithm of --file-hash,
+ * tools/src/mkdwarfs_main.cpp:593-594, by dwarfs::checksum's names).
+ *
+ * Digests are in DwarFS's byte order (checksum_xxh3::finalize,
+ * src/checksum.cpp:185-196): XXH3-64 as its 8 little-endian bytes, XXH3-128 as
+ * low64 little endian followed by high64 little endian (the reverse of
+ * xxhash's canonical form; "Hello, World!" gives
+ * 9553D72C8403DB7750DD474484F21D53), SHA-512/256 as its 32 bytes.
+ */
+enum rpp_file_hash {
+  RPP_HASH_XXH3_64 = 0,
+  RPP_HASH_XXH3_128 = 1,
+  RPP_HASH_SHA512_256 = 2,
+};
+
+/* "xxh3-64", "xxh3-128", "sha512-256" -> the enum; anything else (NULL too) -> a negative value.  Host only. */
+int rpp_file_hash_algo(const char* name);
+/* 8, 16 or 32; 0 for a value that is no algorithm.  Host only. */
+int rpp_file_hash_digest_bytes(int algo);
+
+/*
+ * XXH3-128 (seed 0, default secret, every length class) of the messages of
+ * rpp_xxh3_64_batch, its sibling: d_digest[16 * b ..] receives 16 bytes.
+ * Messages over 240 bytes take one wave each -- the loop of XXH3-64 with a
+ * second final merge -- shorter ones one lane each.
+ */
+int rpp_xxh3_128_batch(const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes, uint32_t n,
+                       const uint8_t* d_prefix, const uint32_t* d_prefix_len, uint8_t* d_digest, void* stream);
+
+/*
+ * File b = d_data[d_offsets[b], d_offsets[b] + d_sizes[b]) hashed with `algo`
+ * into d_digest[digest_bytes * b ..], tightly packed.  d_select (NULL: every
+ * file): a file whose byte is 0 is not read and its digest bytes are not
+ * written.  An unknown algo is RPP_INVALID_ARGUMENT.
+ */
+int rpp_file_hash_batch(int algo, const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                        const uint8_t* d_select, uint32_t n, uint8_t* d_digest, void* stream);
+
+/*
+ * Groups n keys, key b = d_sizes[b] plus the digest_bytes (0, 8, 16 or 32)
+ * bytes at d_digest + digest_bytes * b (d_digest NULL or digest_bytes 0: the
+ * size alone).  d_first[b] = the smallest a <= b with key a == key b;
+ * d_multi[b] (may be NULL) = 1 if key b occurs more than once, else 0.  Keys
+ * with d_select[b] == 0 (d_select NULL: none) take no part: first[b] = b,
+ * multi[b] = 0, their digest is not read.  The result does not depend on
+ * scheduling.  d_workspace holds rpp_group_workspace_bytes(n) bytes (a table
+ * of 32-bit slots, 4-aligned); a smaller one, or n above 2^30, is
+ * RPP_INVALID_ARGUMENT.
+ *
+ * rpp_group_start_slot (host, for tests): the slot at which the probe
+ * sequence of a key starts in the table for n keys.
+ */
+uint64_t rpp_group_workspace_bytes(uint32_t n);
+int rpp_group_first_batch(const uint64_t* d_sizes, const uint8_t* d_digest, uint32_t digest_bytes,
+                          const uint8_t* d_select, uint32_t n, uint32_t* d_first, uint8_t* d_multi,
+                          void* d_workspace, uint64_t workspace_bytes, void* stream);
+uint64_t rpp_group_start_slot(uint64_t size, const uint8_t* digest, uint32_t digest_bytes, uint32_t n);
+
+/*
+ * The scanner's whole decision for n files in one asynchronous sequence:
+ * start hashes (XXH3-64 of the first 4 KiB of every file of 1 MiB and up, 0
+ * below: kLargeFileThreshold, kLargeFileStartHashSize, file_scanner.cpp:59-60);
+ * d_hashed[b] = 1 exactly when another file shares file b's (size, start
+ * hash); those files are hashed with `algo` into d_digest[digest_bytes * b ..]
+ * (the others' digest bytes are left untouched); d_first[b] = the first file
+ * with file b's (size, digest), b itself for a file that was not hashed.
+ * d_workspace holds rpp_file_dedup_workspace_bytes(n) bytes, 16-aligned.
+ */
+uint64_t rpp_file_dedup_workspace_bytes(uint32_t n);
+int rpp_file_dedup_batch(int algo, const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                         uint32_t n, uint8_t* d_digest, uint32_t* d_first, uint8_t* d_hashed, void* d_workspace,
+                         uint64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,7 @@
 #include <span>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "ricepp_amd.h"
@@ -258,6 +259,24 @@ std::vector<uint8_t> make_sections(std::span<std::span<uint8_t const> const> pay
 std::vector<uint8_t> make_sections(std::vector<std::vector<uint8_t>> const& payloads, uint32_t first_number,
                                    uint16_t type, uint16_t compression);
 std::vector<int> check_sections(std::span<uint8_t const> image, int level);
+
+// ---- duplicate files (src/writer/internal/file_scanner.cpp:274-413) ----
+//
+// find_duplicates: file_scanner_::scan_dedupe's decision for `files` in scan
+// order, made on the GPU (rpp_file_dedup_batch): hashed[b] = 1 when another
+// file shares file b's size and start hash, in which case digests[digest_size
+// * b ..] holds its `algo` hash ("xxh3-64", "xxh3-128", "sha512-256"; DwarFS's
+// byte order) and first[b] is the first file with the same size and hash;
+// first[b] = b and zero digest bytes for a file that was not hashed.  An
+// unknown algorithm throws std::runtime_error.  Takes a pooled device context
+// on the current device, like make_sections.
+struct duplicate_files {
+  std::vector<uint32_t> first;
+  std::vector<uint8_t> hashed;
+  std::vector<uint8_t> digests;
+  size_t digest_size;
+};
+duplicate_files find_duplicates(std::span<std::span<uint8_t const> const> files, std::string_view algo = "xxh3-128");
 
 // ---- facade statistics (tests and benchmarks) ----
 struct facade_stats {
