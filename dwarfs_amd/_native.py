@@ -91,11 +91,24 @@ EXPORTED_SYMBOLS = (
     "rpp_group_start_slot",
     "rpp_file_dedup_workspace_bytes",
     "rpp_file_dedup_batch",
+    "rpp_similarity_kind",
+    "rpp_similarity_state_bytes",
+    "rpp_similarity_digest_bytes",
+    "rpp_similarity_chunk_bytes",
+    "rpp_similarity_update_batch",
+    "rpp_similarity_finalize_batch",
+    "rpp_similarity_hash_workspace_bytes",
+    "rpp_similarity_hash_batch",
+    "rpp_similarity_host_update",
+    "rpp_similarity_host_finalize",
 )
 
 RPP_HASH_XXH3_64 = 0
 RPP_HASH_XXH3_128 = 1
 RPP_HASH_SHA512_256 = 2
+
+RPP_SIMILARITY_NILSIMSA = 0
+RPP_SIMILARITY_HISTOGRAM = 1
 
 
 class RppConfig(C.Structure):
@@ -296,6 +309,26 @@ def lib() -> C.CDLL:
         L.rpp_file_dedup_workspace_bytes.restype = C.c_uint64
         L.rpp_file_dedup_batch.argtypes = [C.c_int, P, P, P, C.c_uint32, P, P, P, P, C.c_uint64, P]
         L.rpp_file_dedup_batch.restype = C.c_int
+        L.rpp_similarity_kind.argtypes = [C.c_char_p]
+        L.rpp_similarity_kind.restype = C.c_int
+        L.rpp_similarity_state_bytes.argtypes = [C.c_int]
+        L.rpp_similarity_state_bytes.restype = C.c_uint64
+        L.rpp_similarity_digest_bytes.argtypes = [C.c_int]
+        L.rpp_similarity_digest_bytes.restype = C.c_int
+        L.rpp_similarity_chunk_bytes.argtypes = []
+        L.rpp_similarity_chunk_bytes.restype = C.c_uint64
+        L.rpp_similarity_update_batch.argtypes = [C.c_int, P, P, P, P, C.c_uint32, P, P]
+        L.rpp_similarity_update_batch.restype = C.c_int
+        L.rpp_similarity_finalize_batch.argtypes = [C.c_int, P, P, C.c_uint32, P, P]
+        L.rpp_similarity_finalize_batch.restype = C.c_int
+        L.rpp_similarity_hash_workspace_bytes.argtypes = [C.c_int, C.c_uint32]
+        L.rpp_similarity_hash_workspace_bytes.restype = C.c_uint64
+        L.rpp_similarity_hash_batch.argtypes = [C.c_int, P, P, P, P, C.c_uint64, C.c_uint32, P, P, P, C.c_uint64, P]
+        L.rpp_similarity_hash_batch.restype = C.c_int
+        L.rpp_similarity_host_update.argtypes = [C.c_int, P, P, C.c_uint64]
+        L.rpp_similarity_host_update.restype = C.c_int
+        L.rpp_similarity_host_finalize.argtypes = [C.c_int, P, P]
+        L.rpp_similarity_host_finalize.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

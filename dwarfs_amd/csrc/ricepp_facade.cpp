@@ -1448,6 +1448,68 @@ duplicate_files find_duplicates(std::span<std::span<uint8_t const> const> files,
   return res;
 }
 
+// ---- similarity hashes (src/writer/internal/inode_manager.cpp:399-537) ----
+//
+// Device buffer layout (all parts 16-aligned): files at 16-aligned offsets |
+// u64 offsets, sizes | digests | has | workspace (the states).
+
+std::string similarity_digests::hexdigest(size_t b) const {
+  static char const digits[] = "0123456789abcdef";
+  std::string s;
+  for (size_t i = digest_size; i-- > 0;) {
+    const uint8_t v = digests.at(digest_size * b + i);
+    s += digits[v >> 4];
+    s += digits[v & 15];
+  }
+  return s;
+}
+
+similarity_digests similarity_hashes(std::span<std::span<uint8_t const> const> files, std::string_view kind,
+                                     uint64_t max_size) {
+  const std::string name{kind};
+  const int k = rpp_similarity_kind(name.c_str());
+  if (k < 0) throw std::runtime_error("ricepp_amd: unknown similarity hash: " + name);
+  similarity_digests res;
+  res.digest_size = static_cast<size_t>(rpp_similarity_digest_bytes(k));
+  const size_t n = files.size();
+  if (n == 0) return res;
+  if (n > (size_t{1} << 30)) throw std::invalid_argument("similarity_hashes: too many files");
+  std::vector<uint64_t> tab(2 * n);  // offsets, sizes
+  size_t file_bytes = 0;
+  for (size_t b = 0; b < n; ++b) {
+    tab[b] = file_bytes;
+    tab[n + b] = files[b].size();
+    file_bytes += align16(files[b].size());
+  }
+  const uint64_t ws_bytes = rpp_similarity_hash_workspace_bytes(k, static_cast<uint32_t>(n));
+  const size_t off_tab = align16(file_bytes), off_dig = align16(off_tab + 2 * n * sizeof(uint64_t)),
+               off_has = align16(off_dig + n * res.digest_size), off_ws = align16(off_has + n);
+  const int dev = current_device();
+  ctx_lease ctx{dev};
+  uint8_t* d = ctx->dev(off_ws + ws_bytes);
+  hipStream_t s = ctx->stream();
+  for (size_t b = 0; b < n; ++b)
+    if (!files[b].empty())
+      hip_check(hipMemcpyAsync(d + tab[b], files[b].data(), files[b].size(), hipMemcpyHostToDevice, s), "H2D file");
+  hip_check(hipMemcpyAsync(d + off_tab, tab.data(), 2 * n * sizeof(uint64_t), hipMemcpyHostToDevice, s),
+            "H2D file table");
+  hip_check(hipMemsetAsync(d + off_dig, 0, n * res.digest_size, s), "clear digests");
+  uint64_t* d_tab = reinterpret_cast<uint64_t*>(d + off_tab);
+  const int st = rpp_similarity_hash_batch(k, d, d_tab, d_tab + n, nullptr, max_size, static_cast<uint32_t>(n),
+                                           d + off_dig, d + off_has, d + off_ws, ws_bytes, s);
+  if (st != RPP_OK) {
+    (void)ctx->drain();  // (the copies issued so far read the caller's memory)
+    throw_status(st);
+  }
+  res.has.resize(n);
+  res.digests.resize(n * res.digest_size);
+  hip_check(hipMemcpyAsync(res.has.data(), d + off_has, n, hipMemcpyDeviceToHost, s), "D2H has");
+  hip_check(hipMemcpyAsync(res.digests.data(), d + off_dig, res.digests.size(), hipMemcpyDeviceToHost, s),
+            "D2H digests");
+  ctx->sync();
+  return res;
+}
+
 // ---- FLAC block codec (src/compression/flac.cpp:215-525) ----
 
 namespace {

@@ -576,6 +576,91 @@ int rpp_file_dedup_batch(int algo, const uint8_t* d_data, const uint64_t* d_offs
                          uint32_t n, uint8_t* d_digest, uint32_t* d_first, uint8_t* d_hashed, void* d_workspace,
                          uint64_t workspace_bytes, void* stream);
 
+/*
+ * Similarity hashes of the inode scan (inode_::scan_full / scan_fragments /
+ * scan_range, src/writer/internal/inode_manager.cpp:399-537): what the fragment
+ * orderer sorts or clusters by.
+ *
+ *   nilsimsa    (src/writer/internal/nilsimsa.cpp) 256 counters; with T the
+ *               published Nilsimsa transition table and
+ *               tran3(a,b,c,n) = ((T[(a+n)&255] ^ (T[b]*(2n+1))) + T[c^T[n]]) & 255,
+ *               the byte w0 at position p of the message and the four bytes
+ *               w1..w4 before it increment the buckets (w0,w1,w2,0) from p = 2,
+ *               (w0,w1,w3,1) (w0,w2,w3,2) from p = 3 and (w0,w1,w4,3) (w0,w2,w4,4)
+ *               (w0,w3,w4,5) (w4,w1,w0,6) (w4,w3,w0,7) from p = 4.  Bit i of the
+ *               32-byte digest (byte i >> 3, bit i & 7: the reference's four
+ *               uint64 words, little endian) is acc[i] > total / 256 with total
+ *               = 0, 1, 4 for sizes below 3, 3, 4 and 8 * size - 28 above.
+ *   similarity  (src/writer/internal/similarity.cpp) val = (val << 8) | byte;
+ *               from p = 3 on, the uint32 counter mix32(val + 0x9e3779b9) >> 24
+ *               is incremented (it wraps).  The digest is the uint32
+ *               b0 << 24 | b1 << 16 | b2 << 8 | b3 of the four buckets with the
+ *               highest counts, ties to the lower index, stored as 4 bytes in
+ *               host order (little endian); an empty message gives 0x00010203.
+ *
+ * Both are sums of per-position increments, so a message's state can be built
+ * from chunks in any order and by several calls.  A state is (8-aligned; all
+ * zero is the initial state, so a memset initialises it; the same bytes on the
+ * host and on the device):
+ *   nilsimsa    uint64 acc[256] | uint64 size | uint8 window[4] (the last four
+ *               bytes in message order, window[3] the latest, zero before the
+ *               start) | 4 bytes of padding                       = 2064 bytes
+ *   similarity  uint32 acc[256] | uint32 val | 4 bytes of padding | uint64 size
+ *                                                                  = 1040 bytes
+ */
+enum rpp_similarity {
+  RPP_SIMILARITY_NILSIMSA = 0,
+  RPP_SIMILARITY_HISTOGRAM = 1, /* "similarity" */
+};
+
+/* "nilsimsa", "similarity" -> the enum; anything else (NULL too) -> a negative value.  Host only. */
+int rpp_similarity_kind(const char* name);
+/* 2064 or 1040; 0 for a value that is no kind.  Host only. */
+uint64_t rpp_similarity_state_bytes(int kind);
+/* 32 or 4; 0 for a value that is no kind.  Host only. */
+int rpp_similarity_digest_bytes(int kind);
+/* The bytes of a message that one workgroup accumulates before it adds its
+ * counts to the state; chunks of one message run on different workgroups. */
+uint64_t rpp_similarity_chunk_bytes(void);
+
+/*
+ * Feeds d_data[d_offsets[b], d_offsets[b] + d_sizes[b]) (any alignment, nothing
+ * outside the span is read: no slack is needed) into state b of d_states
+ * (n states of rpp_similarity_state_bytes(kind) bytes, back to back).
+ * Successive calls on one state hash the concatenation of their spans
+ * (scan_range's chunks, scan_fragments' ranges).  d_select (NULL: every
+ * message): state b is left untouched where d_select[b] == 0.  Every entry of a
+ * call has a state of its own: two entries of one call must not share a state
+ * (feed them by two calls).  Sizes are read on the device; asynchronous on
+ * `stream`, graph-capturable; the state does not depend on scheduling.
+ */
+int rpp_similarity_update_batch(int kind, const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                                const uint8_t* d_select, uint32_t n, void* d_states, void* stream);
+
+/* d_digests[digest_bytes * b ..] = the digest of state b (rows with
+ * d_select[b] == 0 are not written).  The states are left unchanged. */
+int rpp_similarity_finalize_batch(int kind, const void* d_states, const uint8_t* d_select, uint32_t n,
+                                  uint8_t* d_digests, void* stream);
+
+/*
+ * scan_full in one asynchronous sequence: fresh states in the workspace,
+ * update, finalize.  A file with d_select[b] == 0, or larger than max_size when
+ * max_size != 0 (the reference's cmp_greater(size, max)), is not read:
+ * d_has[b] = 0 and its digest row is left as it was; every other file gets
+ * d_has[b] = 1.  d_workspace holds rpp_similarity_hash_workspace_bytes(kind, n)
+ * bytes, 8-aligned; a smaller one is RPP_INVALID_ARGUMENT.
+ */
+uint64_t rpp_similarity_hash_workspace_bytes(int kind, uint32_t n);
+int rpp_similarity_hash_batch(int kind, const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                              const uint8_t* d_select, uint64_t max_size, uint32_t n, uint8_t* d_digests,
+                              uint8_t* d_has, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/* The same hashes on the host, in plain C++ over the same state layout (host
+ * memory): what a caller without a GPU uses, and what the device states are
+ * compared with byte for byte. */
+int rpp_similarity_host_update(int kind, void* state, const uint8_t* data, uint64_t size);
+int rpp_similarity_host_finalize(int kind, const void* state, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -278,6 +278,25 @@ struct duplicate_files {
 };
 duplicate_files find_duplicates(std::span<std::span<uint8_t const> const> files, std::string_view algo = "xxh3-128");
 
+// ---- similarity hashes (src/writer/internal/inode_manager.cpp:399-537) ----
+//
+// similarity_hashes: inode_::scan_full's hash of every file, made on the GPU
+// (rpp_similarity_hash_batch): digests[digest_size * b ..] holds file b's
+// `kind` hash ("nilsimsa": 32 bytes, the reference's four uint64 words little
+// endian; "similarity": the uint32 value, little endian).  With max_size != 0 a
+// file larger than max_size is not hashed: has[b] = 0 and zero digest bytes.
+// hexdigest(b) is the digest as the reference's tests print it (the bytes
+// reversed).  An unknown kind throws std::runtime_error.  Takes a pooled device
+// context on the current device, like find_duplicates.
+struct similarity_digests {
+  std::vector<uint8_t> digests;
+  std::vector<uint8_t> has;
+  size_t digest_size;
+  std::string hexdigest(size_t b) const;
+};
+similarity_digests similarity_hashes(std::span<std::span<uint8_t const> const> files,
+                                     std::string_view kind = "nilsimsa", uint64_t max_size = 0);
+
 // ---- facade statistics (tests and benchmarks) ----
 struct facade_stats {
   uint64_t encode_launches, encode_blocks, decode_launches, decode_blocks;
