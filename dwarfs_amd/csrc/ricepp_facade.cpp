@@ -1724,7 +1724,11 @@ bool flac_block_decompressor::decompress_frame(size_t) {
     ctx->sync();
     const uint64_t found = static_cast<uint32_t>(res[1]);
     if (found > max_cand) {
-      if (attempt > 0 || too_wide(found)) throw fail(std::to_string(found) + " frame candidates");
+      // (the second pass: the slots may take the bound above or, for the small
+      // blocks where that is only a few hundred candidates, 64 MiB)
+      const uint64_t slot = max_bs * channels * (bits == 32 ? 8 : 4);
+      if (attempt > 0 || (too_wide(found) && (found + 64) * slot > (64ull << 20)))
+        throw fail(std::to_string(found) + " frame candidates");
       max_cand = found + 64;
       continue;
     }

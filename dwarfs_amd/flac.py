@@ -13,11 +13,13 @@ samples on the device (rpp_pcm_unpack, the pcm_sample_transformer of
 flac.cpp:322-334) and 4096-sample FLAC frames (rpp_flac_encode); decoding runs
 the other way (rpp_flac_decode, rpp_pcm_pack).
 
-Parity unpinned: the reference uses libFLAC (absent here), whose model search
-(LPC orders, precision, apodization) decides its bytes; this encoder writes
-valid FLAC with fixed and LPC predictors chosen by its own search, so its
-streams differ from libFLAC's.  The decoder reads every frame kind RFC 9639
-defines.  ``level`` selects libFLAC's preset limits (levels 0-2 fixed
+FLAC decode is pinned to libFLAC 1.3.3 by the three RFC 9639 Appendix D
+streams and their MD5s (tests/golden/flac_rfc9639.json); the encoder is pinned
+to the format by an independent RFC 9639 reader (tests/flac_ref.py); it is not
+pinned bit-for-bit to libFLAC's encoder choices, and this remains unpinned:
+libFLAC's model search (LPC orders, precision, apodization) decides its bytes,
+and this encoder writes valid FLAC with fixed and LPC predictors chosen by its
+own search.  The decoder reads every frame kind RFC 9639 defines.  ``level`` selects libFLAC's preset limits (levels 0-2 fixed
 predictors only, 3 LPC up to order 6, 4-6 up to 8, 7-8 up to 12) and
 ``exhaustive`` codes every LPC order instead of the estimated best
 (rpp_flac_encode_ex; flac.cpp:312-313).
@@ -267,8 +269,12 @@ class FlacBlockDecompressor:
         return body, channels, bits, nbytes, n, max_bs, max_cand
 
     @staticmethod
-    def _more_candidates(found: int, n: int, max_bs: int) -> int:
-        if found * max_bs > 4 * n + 128 * max_bs:  # (a stream full of false sync codes)
+    def _more_candidates(found: int, n: int, max_bs: int, channels: int, bits: int) -> int:
+        """The candidate table for the second pass.  Every candidate has a scratch slot of max_bs samples per
+        channel: the slots may take 4x the block's samples + 128 slots (the bound of _plan) or, for the small
+        blocks where that is only a few hundred candidates, 64 MiB."""
+        slot = max_bs * channels * (8 if bits == 32 else 4)
+        if found * max_bs > 4 * n + 128 * max_bs and (found + 64) * slot > 64 << 20:  # (a stream full of false sync codes)
             raise RuntimeError(f"[FLAC] failed to process frame: {found} frame candidates")
         return found + 64  # (more sync candidates than estimated: again, with room for all)
 
@@ -301,7 +307,7 @@ class FlacBlockDecompressor:
             found = int(ncand.item())
             if found <= max_cand:
                 break
-            max_cand = self._more_candidates(found, n, max_bs)
+            max_cand = self._more_candidates(found, n, max_bs, channels, bits)
         return self._finish(x, int(status.item()), nbytes)
 
 
@@ -350,7 +356,8 @@ def decompress_many(blocks, device="cuda") -> list:
         if not over.any():
             break
         for k in np.nonzero(over)[0]:
-            mc[k] = FlacBlockDecompressor._more_candidates(int(found[k]), int(ns[k]), int(mbs[k]))
+            mc[k] = FlacBlockDecompressor._more_candidates(int(found[k]), int(ns[k]), int(mbs[k]), int(ch[k]),
+                                                           int(bp[k]))
     st = status.cpu().numpy()
     for k, i in enumerate(live):
         lo = int(out_off[k])

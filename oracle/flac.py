@@ -1,8 +1,12 @@
 """ctypes wrapper around the CPU FLAC restatement (oracle/flac_oracle.c).
 
-TEST INFRASTRUCTURE ONLY (parity unpinned: libFLAC, the reference's FLAC
-coder, is absent -- see the C file's header).  Never imported by the product
-package ``dwarfs_amd``.
+TEST INFRASTRUCTURE ONLY.  Never imported by the product package
+``dwarfs_amd``.
+
+FLAC decode is pinned to libFLAC 1.3.3 by the three RFC 9639 Appendix D
+streams and their MD5s (tests/golden/flac_rfc9639.json); the encoder is pinned
+to the format by an independent RFC 9639 reader (tests/flac_ref.py); it is not
+pinned bit-for-bit to libFLAC's encoder choices, and this remains unpinned.
 """
 
 from __future__ import annotations

@@ -103,11 +103,13 @@ static void roundtrip(ricepp_amd::codec_config const& c, size_t n, unsigned full
 
 int bench(int argc, char** argv);
 int exit_in_flight();
+int flac_decompress_file(char const* in, char const* out);
 void flac_tests();
 
 int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "--bench") return bench(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "--exit-in-flight") return exit_in_flight();
+  if (argc > 3 && std::string(argv[1]) == "--flac-decompress") return flac_decompress_file(argv[2], argv[3]);
   // the batch queue's error paths (round-2 review): the first pooled context
   // fails to come up; the callers of that batch get an exception, none hangs,
   // and the queue and pool work afterwards
@@ -746,5 +748,33 @@ void flac_tests() {
     std::vector<uint8_t> bad(block.begin(), block.begin() + 12);
     bad.resize(40, 0);
     CHECK(throws<std::runtime_error>([&] { flac_block_decompressor d{bad}; }));
+  }
+}
+
+// ---- one FLAC block from a file (facade_test --flac-decompress block out) ----
+// flac_block_decompressor::decompress of the file's bytes, the PCM written to
+// `out`; exit status 3 and the message on stdout when the decompressor throws.
+int flac_decompress_file(char const* in, char const* out) {
+  std::vector<uint8_t> block;
+  if (FILE* f = std::fopen(in, "rb")) {
+    uint8_t buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) block.insert(block.end(), buf, buf + n);
+    std::fclose(f);
+  } else {
+    std::printf("flac-decompress: cannot read %s\n", in);
+    return 2;
+  }
+  try {
+    auto pcm = ricepp_amd::flac_block_decompressor::decompress(block);
+    FILE* f = std::fopen(out, "wb");
+    if (!f || std::fwrite(pcm.data(), 1, pcm.size(), f) != pcm.size() || std::fclose(f) != 0) {
+      std::printf("flac-decompress: cannot write %s\n", out);
+      return 2;
+    }
+    std::printf("flac-decompress: OK %zu bytes\n", pcm.size());
+    return 0;
+  } catch (std::runtime_error const& e) {
+    std::printf("flac-decompress: error: %s\n", e.what());
+    return 3;
   }
 }

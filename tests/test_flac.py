@@ -2,9 +2,11 @@
 round-trips every subframe kind and option it writes, and the library's
 framing (C ABI, no GPU compute) agrees with it.
 
-Parity unpinned: libFLAC, the reference's FLAC coder
-(src/compression/flac.cpp), is absent here and the reference holds no FLAC
-fixture; see oracle/flac_oracle.c.  The data shapes follow
+FLAC decode is pinned to libFLAC 1.3.3 by the three RFC 9639 Appendix D
+streams and their MD5s (tests/golden/flac_rfc9639.json); the encoder is pinned
+to the format by an independent RFC 9639 reader (tests/flac_ref.py); it is not
+pinned bit-for-bit to libFLAC's encoder choices, and this remains unpinned
+(test_flac_conformance.py).  The data shapes follow
 test/flac_compressor_test.cpp:97-113 (sines of 599 (c + 1) mod 256 * 3.1
 samples period per channel)."""
 

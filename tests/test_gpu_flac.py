@@ -1,6 +1,9 @@
 """FLAC block codec on the GPU (dwarfs_amd.flac over rpp_flac_encode /
-rpp_flac_decode).  Parity unpinned (libFLAC absent, no FLAC fixture in the
-reference): every GPU stream is decoded by the CPU restatement
+rpp_flac_decode).  FLAC decode is pinned to libFLAC 1.3.3 by the three
+RFC 9639 Appendix D streams and their MD5s (tests/golden/flac_rfc9639.json);
+the encoder is pinned to the format by an independent RFC 9639 reader
+(tests/flac_ref.py); it is not pinned bit-for-bit to libFLAC's encoder
+choices, and this remains unpinned (test_gpu_flac_conformance.py).  Here every GPU stream is decoded by the CPU restatement
 (oracle/flac_oracle.c) as well as by the GPU, and the GPU decoder reads the
 restatement's streams of every subframe kind.  The matrix is the reference's
 own (test/flac_compressor_test.cpp:138-205: endianness x signedness x padding
@@ -247,8 +250,8 @@ def test_reference_pcm_fixtures_round_trip(fx):
     """The reference's real PCM fixtures (test/pcmaudio/test{8,12,16,20,24,32}.{wav,aiff}) with the metadata the
     pcmaudio categorizer emits for them (tests/golden/pcmaudio_fixtures.json) through flac_block_compressor /
     flac_block_decompressor on the GPU: exact bytes back, the metadata carried in the block header, and the GPU's
-    FLAC stream decoded by the CPU restatement to the samples the transformer unpacks.  Parity unpinned: no
-    libFLAC output exists to compare the stream itself with."""
+    FLAC stream decoded by the CPU restatement to the samples the transformer unpacks.  The encoder's bytes are not
+    pinned to libFLAC's encoder choices."""
     from oracle import oracle as O
     m = fx["metadata"]
     pcm = bytes.fromhex(fx["pcm_hex"])
