@@ -101,6 +101,21 @@ EXPORTED_SYMBOLS = (
     "rpp_similarity_hash_batch",
     "rpp_similarity_host_update",
     "rpp_similarity_host_finalize",
+    "rpp_segment_check_config",
+    "rpp_segment_tile_frames",
+    "rpp_segment_positions",
+    "rpp_segment_index_slots",
+    "rpp_segment_hash_workspace_bytes",
+    "rpp_segment_hash_batch",
+    "rpp_segment_scan_workspace_bytes",
+    "rpp_segment_scan_batch",
+    "rpp_segment_index_workspace_bytes",
+    "rpp_segment_index_batch",
+    "rpp_segment_extend_batch",
+    "rpp_segment_host_hashes",
+    "rpp_segment_host_index",
+    "rpp_segment_host_scan",
+    "rpp_segment_host_extend",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -193,6 +208,22 @@ class RppSectionHeader(C.Structure):
         ("major", C.c_uint8),
         ("minor", C.c_uint8),
     ]
+
+
+class RppSegmentConfig(C.Structure):
+    """``rpp_segment_config``."""
+
+    _fields_ = [
+        ("window_bits", C.c_uint32),
+        ("increment_shift", C.c_uint32),
+        ("granularity", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("filter_bits", C.c_uint64),
+    ]
+
+
+class RppSegmentScanResult(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_uint32)]
 
 
 _lib = None
@@ -329,6 +360,39 @@ def lib() -> C.CDLL:
         L.rpp_similarity_host_update.restype = C.c_int
         L.rpp_similarity_host_finalize.argtypes = [C.c_int, P, P]
         L.rpp_similarity_host_finalize.restype = C.c_int
+        SC = C.POINTER(RppSegmentConfig)
+        L.rpp_segment_check_config.argtypes = [SC]
+        L.rpp_segment_check_config.restype = C.c_int
+        L.rpp_segment_tile_frames.argtypes = []
+        L.rpp_segment_tile_frames.restype = C.c_uint64
+        L.rpp_segment_positions.argtypes = [SC, C.c_uint64]
+        L.rpp_segment_positions.restype = C.c_uint64
+        L.rpp_segment_index_slots.argtypes = [SC, C.c_uint64]
+        L.rpp_segment_index_slots.restype = C.c_uint64
+        L.rpp_segment_hash_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
+        L.rpp_segment_hash_workspace_bytes.restype = C.c_uint64
+        L.rpp_segment_hash_batch.argtypes = [SC, P, P, P, C.c_uint32, C.c_uint64, P, C.c_uint64, P, P, P, C.c_uint64, P]
+        L.rpp_segment_hash_batch.restype = C.c_int
+        L.rpp_segment_scan_workspace_bytes.argtypes = [C.c_uint32, C.c_uint64]
+        L.rpp_segment_scan_workspace_bytes.restype = C.c_uint64
+        L.rpp_segment_scan_batch.argtypes = [SC, P, P, P, C.c_uint32, C.c_uint64, P, P, C.c_uint64, P, P, P, C.c_uint64,
+                                             P]
+        L.rpp_segment_scan_batch.restype = C.c_int
+        L.rpp_segment_index_workspace_bytes.argtypes = [C.c_uint32]
+        L.rpp_segment_index_workspace_bytes.restype = C.c_uint64
+        L.rpp_segment_index_batch.argtypes = [SC, P, P, P, C.c_uint32, C.c_uint64, P, P, P, C.c_uint64, P, P, P, P, P,
+                                              C.c_uint64, P]
+        L.rpp_segment_index_batch.restype = C.c_int
+        L.rpp_segment_extend_batch.argtypes = [SC, P, P, P, C.c_uint32, P, P]
+        L.rpp_segment_extend_batch.restype = C.c_int
+        L.rpp_segment_host_hashes.argtypes = [SC, P, C.c_uint64, P]
+        L.rpp_segment_host_hashes.restype = C.c_int
+        L.rpp_segment_host_index.argtypes = [SC, P, C.c_uint64, P, P, P, P, P]
+        L.rpp_segment_host_index.restype = C.c_int
+        L.rpp_segment_host_scan.argtypes = [SC, P, C.c_uint64, P, P, C.c_uint64, P]
+        L.rpp_segment_host_scan.restype = C.c_int
+        L.rpp_segment_host_extend.argtypes = [SC, P, P, P, C.c_uint32, P]
+        L.rpp_segment_host_extend.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

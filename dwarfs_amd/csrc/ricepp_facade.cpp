@@ -1510,6 +1510,121 @@ similarity_digests similarity_hashes(std::span<std::span<uint8_t const> const> f
   return res;
 }
 
+// ---- segmenter match search (src/writer/segmenter.cpp) ----
+//
+// Device buffer layout (all parts 16-aligned): the block or extent | u64
+// offset, size | the outputs | workspace.
+
+namespace {
+
+rpp_segment_config segment_native(segment_config const& cfg) {
+  rpp_segment_config c{cfg.window_bits, cfg.increment_shift, cfg.granularity, 0, cfg.filter_bits};
+  const int st = rpp_segment_check_config(&c);
+  if (st != RPP_OK) throw_status(st);
+  return c;
+}
+
+}  // namespace
+
+segment_block_index segment_index(std::span<uint8_t const> block, segment_config const& cfg) {
+  const rpp_segment_config c = segment_native(cfg);
+  const uint64_t frames = block.size() / cfg.granularity, words = cfg.filter_bits / 64;
+  if (frames >= (uint64_t{1} << 32)) throw std::invalid_argument("segment_index: block too large");
+  const uint64_t slots = rpp_segment_index_slots(&c, frames);
+  segment_block_index res;
+  res.filter.assign(words, 0);
+  if (slots == 0) return res;
+  const uint64_t ws_bytes = rpp_segment_index_workspace_bytes(1);
+  const size_t off_tab = align16(block.size()), off_hash = off_tab + 16, off_off = off_hash + align16(4 * slots),
+               off_ent = off_off + align16(4 * slots), off_start = off_ent + align16(slots), off_bf = off_start + 16,
+               off_gf = off_bf + 8 * words, off_st = off_gf + 8 * words, off_ws = off_st + 16;
+  const int dev = current_device();
+  ctx_lease ctx{dev};
+  uint8_t* d = ctx->dev(off_ws + ws_bytes);
+  hipStream_t s = ctx->stream();
+  const uint64_t tab[2] = {0, frames};
+  hip_check(hipMemcpyAsync(d, block.data(), block.size(), hipMemcpyHostToDevice, s), "H2D block");
+  hip_check(hipMemcpyAsync(d + off_tab, tab, sizeof tab, hipMemcpyHostToDevice, s), "H2D block table");
+  hip_check(hipMemsetAsync(d + off_bf, 0, 16 * words, s), "clear filters");
+  uint64_t* d_tab = reinterpret_cast<uint64_t*>(d + off_tab);
+  const int st = rpp_segment_index_batch(
+      &c, d, d_tab, d_tab + 1, 1, frames, reinterpret_cast<uint32_t*>(d + off_hash),
+      reinterpret_cast<uint32_t*>(d + off_off), d + off_ent, slots, reinterpret_cast<uint64_t*>(d + off_start),
+      reinterpret_cast<uint64_t*>(d + off_bf), reinterpret_cast<uint64_t*>(d + off_gf),
+      reinterpret_cast<int32_t*>(d + off_st), d + off_ws, ws_bytes, s);
+  if (st != RPP_OK) {
+    (void)ctx->drain();  // (the copies issued so far read the caller's memory)
+    throw_status(st);
+  }
+  res.hash.resize(slots);
+  res.offset.resize(slots);
+  res.entered.resize(slots);
+  int32_t dst = 0;
+  hip_check(hipMemcpyAsync(res.hash.data(), d + off_hash, 4 * slots, hipMemcpyDeviceToHost, s), "D2H hash");
+  hip_check(hipMemcpyAsync(res.offset.data(), d + off_off, 4 * slots, hipMemcpyDeviceToHost, s), "D2H offset");
+  hip_check(hipMemcpyAsync(res.entered.data(), d + off_ent, slots, hipMemcpyDeviceToHost, s), "D2H entered");
+  hip_check(hipMemcpyAsync(res.filter.data(), d + off_bf, 8 * words, hipMemcpyDeviceToHost, s), "D2H filter");
+  hip_check(hipMemcpyAsync(&dst, d + off_st, 4, hipMemcpyDeviceToHost, s), "D2H status");
+  ctx->sync();
+  if (dst != RPP_OK) throw_status(dst);
+  return res;
+}
+
+segment_hits segment_scan(std::span<uint8_t const> extent, std::span<uint64_t const> filter,
+                          segment_config const& cfg) {
+  const rpp_segment_config c = segment_native(cfg);
+  const uint64_t frames = extent.size() / cfg.granularity, words = cfg.filter_bits / 64;
+  if (filter.size() != words) throw std::invalid_argument("segment_scan: the filter must hold filter_bits / 64 words");
+  if (frames >= (uint64_t{1} << 32)) throw std::invalid_argument("segment_scan: extent too large");
+  segment_hits res;
+  const uint64_t npos = rpp_segment_positions(&c, frames);
+  if (npos == 0) return res;
+  const uint64_t ws_bytes = rpp_segment_scan_workspace_bytes(1, frames);
+  const int dev = current_device();
+  ctx_lease ctx{dev};
+  hipStream_t s = ctx->stream();
+  uint64_t capacity = std::max<uint64_t>(1024, npos / 64);
+  for (int attempt = 0;; ++attempt) {
+    const size_t off_tab = align16(extent.size()), off_filter = off_tab + 16, off_res = off_filter + align16(8 * words),
+                 off_hits = off_res + 16, off_ws = off_hits + align16(8 * capacity);
+    uint8_t* d = ctx->dev(off_ws + ws_bytes);
+    const uint64_t tab[2] = {0, frames};
+    hip_check(hipMemcpyAsync(d, extent.data(), extent.size(), hipMemcpyHostToDevice, s), "H2D extent");
+    hip_check(hipMemcpyAsync(d + off_tab, tab, sizeof tab, hipMemcpyHostToDevice, s), "H2D extent table");
+    hip_check(hipMemcpyAsync(d + off_filter, filter.data(), 8 * words, hipMemcpyHostToDevice, s), "H2D filter");
+    uint64_t* d_tab = reinterpret_cast<uint64_t*>(d + off_tab);
+    const int st = rpp_segment_scan_batch(&c, d, d_tab, d_tab + 1, 1, frames,
+                                          reinterpret_cast<uint64_t*>(d + off_filter),
+                                          reinterpret_cast<rpp_segment_hit*>(d + off_hits), capacity, nullptr,
+                                          reinterpret_cast<rpp_segment_scan_result*>(d + off_res), d + off_ws,
+                                          ws_bytes, s);
+    if (st != RPP_OK) {
+      (void)ctx->drain();
+      throw_status(st);
+    }
+    rpp_segment_scan_result r{};
+    hip_check(hipMemcpyAsync(&r, d + off_res, sizeof r, hipMemcpyDeviceToHost, s), "D2H scan result");
+    ctx->sync();
+    if (r.status == RPP_OUTPUT_TOO_SMALL && attempt == 0) {
+      capacity = r.count;
+      continue;
+    }
+    if (r.status != RPP_OK) throw_status(r.status);
+    std::vector<rpp_segment_hit> hits(r.count);
+    if (r.count) {
+      hip_check(hipMemcpyAsync(hits.data(), d + off_hits, 8 * r.count, hipMemcpyDeviceToHost, s), "D2H hits");
+      ctx->sync();
+    }
+    res.pos.resize(r.count);
+    res.hash.resize(r.count);
+    for (size_t i = 0; i < hits.size(); ++i) {
+      res.pos[i] = hits[i].pos;
+      res.hash[i] = hits[i].hash;
+    }
+    return res;
+  }
+}
+
 // ---- FLAC block codec (src/compression/flac.cpp:215-525) ----
 
 namespace {

@@ -661,6 +661,155 @@ int rpp_similarity_hash_batch(int kind, const uint8_t* d_data, const uint64_t* d
 int rpp_similarity_host_update(int kind, void* state, const uint8_t* data, uint64_t size);
 int rpp_similarity_host_finalize(int kind, const void* state, uint8_t* out);
 
+/*
+ * The segmenter's match search (src/writer/segmenter.cpp,
+ * include/dwarfs/writer/internal/cyclic_hash.h): the three data-parallel parts
+ * of segment_and_add_data.  Choosing among matches, emitting chunks, appending
+ * to blocks and the look-back bookkeeping stay with the caller; candidates come
+ * from the index as it stands when a scan is launched.
+ *
+ *   frames   a frame is `granularity` (g) bytes; W = 1 << window_bits frames,
+ *            L = W * g bytes, step = max(1, W >> increment_shift) frames.
+ *   hash     of the window at frame p: over the bytes x_i = data[p g + i],
+ *            a = sum x_i, b = sum (L - i) x_i, both mod 2^16; the value is
+ *            a | b << 16 (rsync_hash; sliding by a byte is a += in - out,
+ *            b += a - L out).
+ *   filter   filter_bits = 2^k >= 64 bits: bit h & 63 of the uint64 word
+ *            (h >> 6) & (words - 1); the same bytes on the host and on the
+ *            device (little endian).
+ *   index    of a block of F frames: slot j = 0 .. (F - W) / step holds the
+ *            window at frame offset j * step (the reference's slot m = j + W /
+ *            step, offset m * step - W) and its hash.  A slot is entered unless
+ *            its window is L equal bytes v and an earlier slot of the same
+ *            block holds an all-v window (is_existing_repeating_sequence, by
+ *            content).  Every entered hash is ORed into the block's filter and
+ *            into the global filter.
+ *   scan     every position p in 0 .. n - W of an extent of n frames whose hash
+ *            tests positive in the filter, as (p, hash), in ascending p.
+ *   extend   segment_match::verify_and_extend, see rpp_segment_extend_batch.
+ *
+ * window_bits outside 1..20, a granularity outside 1..64 or a filter_bits that
+ * is not a power of two in 64 .. 2^32 is RPP_UNSUPPORTED_CONFIG.  An extent or
+ * block must be shorter than 2^32 frames.
+ */
+typedef struct rpp_segment_config {
+  uint32_t window_bits;
+  uint32_t increment_shift;
+  uint32_t granularity;
+  uint32_t reserved;
+  uint64_t filter_bits;
+} rpp_segment_config;
+
+typedef struct rpp_segment_hit {
+  uint32_t pos; /* frames from the start of the extent */
+  uint32_t hash;
+} rpp_segment_hit;
+
+typedef struct rpp_segment_scan_result {
+  uint64_t count;  /* hits found, also beyond the capacity */
+  int32_t status;  /* RPP_OK; RPP_OUTPUT_TOO_SMALL: count > capacity; RPP_INVALID_ARGUMENT: see below */
+  uint32_t reserved;
+} rpp_segment_scan_result;
+
+/* All in frames; the extent's bytes start at extent_offset of the extent data,
+ * the block's at block_offset of the block data. */
+typedef struct rpp_segment_candidate {
+  uint64_t extent_offset;
+  uint64_t block_offset;
+  uint32_t pos;          /* the hit in the extent */
+  uint32_t off;          /* the slot's offset in the block */
+  uint32_t begin, end;   /* the extent's frames the match may cover */
+  uint32_t block_frames; /* frames in the block */
+  uint32_t reserved;
+} rpp_segment_candidate;
+
+typedef struct rpp_segment_match {
+  uint32_t off, pos, size; /* size 0: no match, off and pos as given */
+} rpp_segment_match;
+
+int rpp_segment_check_config(const rpp_segment_config* cfg);
+/* Positions one workgroup hashes; an extent is cut into tiles of this many. */
+uint64_t rpp_segment_tile_frames(void);
+/* frames - W + 1 window positions, (frames - W) / step + 1 slots; 0 for a
+ * shorter (or too long) extent or block and for a bad config.  Host only. */
+uint64_t rpp_segment_positions(const rpp_segment_config* cfg, uint64_t frames);
+uint64_t rpp_segment_index_slots(const rpp_segment_config* cfg, uint64_t frames);
+
+/*
+ * Extent b is d_data[d_offsets[b], d_offsets[b] + d_sizes[b] * g): offsets in
+ * bytes (any alignment), sizes in frames, both read on the device; nothing
+ * outside an extent is read.  total_frames is a host-side upper bound of the
+ * sum of the sizes (it sizes the workspace and the launch).  Asynchronous on
+ * `stream`, no host round trip, graph-capturable.  Workspaces are 16-aligned.
+ *
+ * hash_batch: d_hashes[d_hash_start[b] + p] = the hash at position p of extent
+ * b; d_hash_start (n + 1 entries, written) is the exclusive scan of the extents'
+ * position counts.  *d_status is RPP_OK, RPP_OUTPUT_TOO_SMALL (more positions
+ * than hash_capacity) or RPP_INVALID_ARGUMENT (an extent of 2^32 frames or
+ * more, or sizes beyond total_frames); with an error nothing else is written.
+ */
+uint64_t rpp_segment_hash_workspace_bytes(uint32_t n, uint64_t total_frames);
+int rpp_segment_hash_batch(const rpp_segment_config* cfg, const uint8_t* d_data, const uint64_t* d_offsets,
+                           const uint64_t* d_sizes, uint32_t n, uint64_t total_frames, uint32_t* d_hashes,
+                           uint64_t hash_capacity, uint64_t* d_hash_start, int32_t* d_status, void* d_workspace,
+                           uint64_t workspace_bytes, void* stream);
+
+/*
+ * scan_batch: the hits of extent b are d_hits[d_hit_start[b] .. d_hit_start[b +
+ * 1]), ascending in p (d_hit_start: n + 1 entries, may be NULL).  At most
+ * `capacity` hits are written, the first ones; d_result->count is the full
+ * count and d_result->status tells an overflow.  The order and the bytes do
+ * not depend on scheduling.
+ */
+uint64_t rpp_segment_scan_workspace_bytes(uint32_t n, uint64_t total_frames);
+int rpp_segment_scan_batch(const rpp_segment_config* cfg, const uint8_t* d_data, const uint64_t* d_offsets,
+                           const uint64_t* d_sizes, uint32_t n, uint64_t total_frames, const uint64_t* d_filter,
+                           rpp_segment_hit* d_hits, uint64_t capacity, uint64_t* d_hit_start,
+                           rpp_segment_scan_result* d_result, void* d_workspace, uint64_t workspace_bytes,
+                           void* stream);
+
+/*
+ * index_batch: block b's slots are entries d_slot_start[b] .. d_slot_start[b +
+ * 1] of d_hash / d_offset (frames) / d_entered (d_slot_start: n + 1 entries,
+ * written).  Entered hashes are ORed into d_block_filters[b * words ..] and
+ * into d_global_filter (words = filter_bits / 64; neither is cleared).
+ * max_block_frames is a host-side upper bound of the block sizes.  *d_status
+ * as for hash_batch, with slot_capacity in place of hash_capacity.
+ */
+uint64_t rpp_segment_index_workspace_bytes(uint32_t n);
+int rpp_segment_index_batch(const rpp_segment_config* cfg, const uint8_t* d_data, const uint64_t* d_offsets,
+                            const uint64_t* d_sizes, uint32_t n, uint64_t max_block_frames, uint32_t* d_hash,
+                            uint32_t* d_offset, uint8_t* d_entered, uint64_t slot_capacity, uint64_t* d_slot_start,
+                            uint64_t* d_block_filters, uint64_t* d_global_filter, int32_t* d_status,
+                            void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/*
+ * extend_batch: for candidate c (a candidate with off + W > block_frames, pos +
+ * W > end or begin > pos is no match and nothing of it is read): if the L
+ * window bytes differ, size = 0; otherwise begin = max(begin, pos - off), end =
+ * min(end, pos + block_frames - off), prefix = the common suffix of
+ * extent[begin, pos) and the block before off, suffix = the common prefix of
+ * extent[pos + W, end) and the block from off + W, both in bytes rounded down
+ * to whole frames; the match is (off - prefix, pos - prefix, W + prefix +
+ * suffix).  Extent frames [begin, end) and the whole block must be readable.
+ */
+int rpp_segment_extend_batch(const rpp_segment_config* cfg, const uint8_t* d_extent_data, const uint8_t* d_block_data,
+                             const rpp_segment_candidate* d_candidates, uint32_t n, rpp_segment_match* d_matches,
+                             void* stream);
+
+/* The same on the host for one extent or block (host memory), written as the
+ * rolling update and a sequential index build.  host_hashes writes
+ * rpp_segment_positions() values, host_index rpp_segment_index_slots() slots
+ * (the filters are ORed into); host_scan returns RPP_OUTPUT_TOO_SMALL when
+ * *count > capacity. */
+int rpp_segment_host_hashes(const rpp_segment_config* cfg, const uint8_t* data, uint64_t frames, uint32_t* out);
+int rpp_segment_host_index(const rpp_segment_config* cfg, const uint8_t* block, uint64_t frames, uint32_t* hash,
+                           uint32_t* offset, uint8_t* entered, uint64_t* block_filter, uint64_t* global_filter);
+int rpp_segment_host_scan(const rpp_segment_config* cfg, const uint8_t* data, uint64_t frames, const uint64_t* filter,
+                          rpp_segment_hit* hits, uint64_t capacity, uint64_t* count);
+int rpp_segment_host_extend(const rpp_segment_config* cfg, const uint8_t* extent_data, const uint8_t* block_data,
+                            const rpp_segment_candidate* candidates, uint32_t n, rpp_segment_match* matches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -297,6 +297,31 @@ struct similarity_digests {
 similarity_digests similarity_hashes(std::span<std::span<uint8_t const> const> files,
                                      std::string_view kind = "nilsimsa", uint64_t max_size = 0);
 
+// ---- segmenter match search (src/writer/segmenter.cpp) ----
+//
+// segment_index: the index of one block as active_block::append_bytes builds
+// it, made on the GPU (rpp_segment_index_batch): per step-aligned window its
+// hash, frame offset and whether it is entered, and the block's bloom filter.
+// segment_scan: the positions of `extent` whose window hash tests positive in
+// `filter` (filter_bits / 64 words), ascending (rpp_segment_scan_batch).  The
+// segmenter's control loop stays with the caller.  A bad configuration throws
+// as the codec's does; both take a pooled device context on the current device.
+struct segment_config {
+  uint32_t window_bits = 12, increment_shift = 1, granularity = 1;
+  uint64_t filter_bits = uint64_t{1} << 16;
+};
+struct segment_block_index {
+  std::vector<uint32_t> hash, offset;
+  std::vector<uint8_t> entered;
+  std::vector<uint64_t> filter;
+};
+struct segment_hits {
+  std::vector<uint32_t> pos, hash;
+};
+segment_block_index segment_index(std::span<uint8_t const> block, segment_config const& cfg);
+segment_hits segment_scan(std::span<uint8_t const> extent, std::span<uint64_t const> filter,
+                          segment_config const& cfg);
+
 // ---- facade statistics (tests and benchmarks) ----
 struct facade_stats {
   uint64_t encode_launches, encode_blocks, decode_launches, decode_blocks;
