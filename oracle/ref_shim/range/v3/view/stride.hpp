@@ -1,0 +1,3 @@
+// range-v3 name over the shim (see ../detail/shim.hpp); test infrastructure only.
+#pragma once
+#include "../detail/shim.hpp"

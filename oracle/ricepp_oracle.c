@@ -10,9 +10,15 @@
  * (mhx/dwarfs, /root/reference/ricepp).  Each function cites the reference
  * file:line it follows.  No reference source is copied.
  *
- * Parity pinning (see DESIGN.md "Oracle"): the reference cannot be built in
- * this image (it needs range-v3, which is absent), so this restatement is
- * pinned by the reference's own fixtures:
+ * Parity pinning (see DESIGN.md "Oracle"): the reference itself, compiled
+ * unmodified by oracle/ref_build.py into oracle/_ref/libdwarfs_ref.so (a small
+ * stand-in for range-v3 under oracle/ref_shim/ is all it lacks), is the ground
+ * truth.  tests/test_reference_parity.py compares this file with it stream for
+ * stream -- the split search of compute_best_split, the raw path and dirty low
+ * bits included -- and tests/golden/reference_kat.json records its answers.
+ * An odd length with two component streams, which the reference's release
+ * build accepts but cannot size a buffer for, is refused here.
+ * Pinned as before by the reference's own fixtures:
  *   - the 4186-byte bitstream KAT of ricepp/test/bitstream_test.cpp:113-1466
  *     (writer and reader, via rpo_bitstream_run_ops),
  *   - the worst-case size KATs of ricepp/test/codec_test.cpp:164-196,
