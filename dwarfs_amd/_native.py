@@ -116,6 +116,17 @@ EXPORTED_SYMBOLS = (
     "rpp_segment_host_index",
     "rpp_segment_host_scan",
     "rpp_segment_host_extend",
+    "rpp_order_check_options",
+    "rpp_order_split_pass_children",
+    "rpp_order_chain_threads",
+    "rpp_order_chain_stage_rows",
+    "rpp_order_split_workspace_bytes",
+    "rpp_order_split_batch",
+    "rpp_order_chain_workspace_bytes",
+    "rpp_order_chain_batch",
+    "rpp_order_host_split",
+    "rpp_order_host_chain",
+    "rpp_order_host_nilsimsa",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -224,6 +235,24 @@ class RppSegmentConfig(C.Structure):
 
 class RppSegmentScanResult(C.Structure):
     _fields_ = [("count", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class RppOrderStats(C.Structure):
+    """``rpp_order_stats``."""
+
+    _fields_ = [
+        ("fallbacks", C.c_uint64),
+        ("fallback_ties", C.c_uint64),
+        ("chain_early_stops", C.c_uint64),
+        ("depth", C.c_uint32),
+        ("leaves", C.c_uint32),
+        ("largest_leaf", C.c_uint32),
+        ("largest_final_leaf", C.c_uint32),
+        ("largest_node", C.c_uint32),
+        ("duplicate_groups", C.c_uint32),
+        ("unique", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
 
 
 _lib = None
@@ -393,6 +422,26 @@ def lib() -> C.CDLL:
         L.rpp_segment_host_scan.restype = C.c_int
         L.rpp_segment_host_extend.argtypes = [SC, P, P, P, C.c_uint32, P]
         L.rpp_segment_host_extend.restype = C.c_int
+        U32, U64 = C.c_uint32, C.c_uint64
+        L.rpp_order_check_options.argtypes = [U32, U32]
+        L.rpp_order_check_options.restype = C.c_int
+        for name in ("rpp_order_split_pass_children", "rpp_order_chain_threads", "rpp_order_chain_stage_rows"):
+            getattr(L, name).argtypes = []
+            getattr(L, name).restype = U32
+        L.rpp_order_split_workspace_bytes.argtypes = [U64]
+        L.rpp_order_split_workspace_bytes.restype = U64
+        L.rpp_order_split_batch.argtypes = [P, U32, P, P, P, U32, U64, U32, U32, P, P, P, U64, P]
+        L.rpp_order_split_batch.restype = C.c_int
+        L.rpp_order_chain_workspace_bytes.argtypes = [U64]
+        L.rpp_order_chain_workspace_bytes.restype = U64
+        L.rpp_order_chain_batch.argtypes = [P, U32, P, P, P, U32, P, P]
+        L.rpp_order_chain_batch.restype = C.c_int
+        L.rpp_order_host_split.argtypes = [P, U32, P, U32, U32, U32, P, P]
+        L.rpp_order_host_split.restype = C.c_int
+        L.rpp_order_host_chain.argtypes = [P, U32, P, P, U32, P]
+        L.rpp_order_host_chain.restype = C.c_int
+        L.rpp_order_host_nilsimsa.argtypes = [P, P, P, U32, P, U32, U32, U32, P, C.POINTER(RppOrderStats)]
+        L.rpp_order_host_nilsimsa.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

@@ -810,6 +810,103 @@ int rpp_segment_host_scan(const rpp_segment_config* cfg, const uint8_t* data, ui
 int rpp_segment_host_extend(const rpp_segment_config* cfg, const uint8_t* extent_data, const uint8_t* block_data,
                             const rpp_segment_candidate* candidates, uint32_t n, rpp_segment_match* matches);
 
+/*
+ * Nilsimsa fragment ordering (src/writer/internal/similarity_ordering.cpp,
+ * --order=nilsimsa): the two distance loops on the device, and the whole
+ * algorithm on the host.
+ *
+ *   elements  n_elems rows of four uint64 words (the 32-byte nilsimsa digest as
+ *             rpp_similarity_hash_batch writes it, read as little-endian words
+ *             w0..w3; 16-aligned on the device), a uint64 size and a uint32
+ *             rank each (all ranks distinct; a precedes b iff rank[a] <
+ *             rank[b]; NULL: the element's own number).
+ *   distance  sum of popcount(a.w[i] ^ b.w[i]).
+ *   split     cluster_by_distance of one node: its elements are visited in list
+ *             order; the first child, in creation order, whose centroid is
+ *             within max_distance takes the element, else a new child while
+ *             there are fewer than max_children, else the child at the smallest
+ *             distance (the earliest at a tie).  Then the child's centroid adds
+ *             the element: member count + 1, the 256 bit counters add the
+ *             element's bits, centroid bit = counter > members / 2.
+ *   chain     order_by_shortest_path over `count` entries with a `from` and a
+ *             `to` row each: for i = 0 .. count - 2, among k = i + 1 .. count -
+ *             1 the first k with distance(from(i), to(k)) <= 1 if there is one,
+ *             else the first k at the minimum, is swapped with entry i + 1.
+ *   order     duplicates, cluster tree from max_distance 128 halving down to 1,
+ *             leaf chains, tree chains, collect: rpp_order_host_nilsimsa.
+ *
+ * The device entry points take lists that are already sorted; sorting,
+ * regrouping a level by (node, child) and the tree bookkeeping are the
+ * caller's.  Asynchronous on `stream`; the results do not depend on
+ * scheduling.  max_children == 0 or max_cluster_size == 0 is
+ * RPP_UNSUPPORTED_CONFIG (fragment_order_parser.cpp:89-97).
+ */
+typedef struct rpp_order_stats {
+  uint64_t fallbacks;          /* elements placed by the full-node rule */
+  uint64_t fallback_ties;      /* ... of them, with two children at the smallest distance */
+  uint64_t chain_early_stops;  /* chain steps that ended on a distance <= 1 */
+  uint32_t depth;              /* split levels, 1 (the root only) .. 8; 0 for an empty index */
+  uint32_t leaves;             /* clusters that were not split again */
+  uint32_t largest_leaf;
+  uint32_t largest_final_leaf; /* the largest leaf made at max_distance == 1 */
+  uint32_t largest_node;       /* the most children of one node */
+  uint32_t duplicate_groups;
+  uint32_t unique;             /* elements left after the duplicates */
+  uint32_t reserved;
+} rpp_order_stats;
+
+int rpp_order_check_options(uint32_t max_children, uint32_t max_cluster_size);
+/* The children one pass of the split compares an element with, the entries one
+ * pass of the chain covers, and the longest segment the chain keeps in LDS. */
+uint32_t rpp_order_split_pass_children(void);
+uint32_t rpp_order_chain_threads(void);
+uint32_t rpp_order_chain_stage_rows(void);
+
+/*
+ * split_batch: node j's elements are d_index[d_node_start[j] .. d_node_start[j +
+ * 1]) (n_nodes + 1 starts).  d_child[slot] = the child, numbered in creation
+ * order, that the element of that slot went to; d_nchildren[j] = the node's
+ * child count.  Node j keeps its children's centroids and counters in child
+ * slots d_child_base[j] .. + min(elements, max_children) of the workspace, which
+ * has child_slots slots = rpp_order_split_workspace_bytes(child_slots) bytes,
+ * 16-aligned, and needs no initialisation; the nodes' slot ranges must not
+ * overlap.  A node whose range does not fit, or that holds an id >= n_elems,
+ * gets d_nchildren[j] = 0xffffffff and nothing outside its own ranges is
+ * touched.  One launch; a tree level depends on the level before, so the
+ * caller launches level by level.  max_distance > 256 is RPP_INVALID_ARGUMENT.
+ */
+uint64_t rpp_order_split_workspace_bytes(uint64_t child_slots);
+int rpp_order_split_batch(const uint64_t* d_bits, uint32_t n_elems, const uint32_t* d_index,
+                          const uint32_t* d_node_start, const uint64_t* d_child_base, uint32_t n_nodes,
+                          uint64_t child_slots, uint32_t max_children, uint32_t max_distance, uint32_t* d_child,
+                          uint32_t* d_nchildren, void* d_workspace, uint64_t workspace_bytes, void* stream);
+
+/*
+ * chain_batch: segment s is entries d_seg_start[s] .. d_seg_start[s + 1]
+ * (n_segments + 1 starts); entry e has the rows d_from_ids[e] and d_to_ids[e]
+ * (the same pointer for a leaf).  d_perm[d_seg_start[s] + i] = the entry,
+ * counted from the segment's start, that the chain leaves at place i.  A
+ * segment of 0 or 1 entries is the identity; one with an id >= n_elems is
+ * filled with 0xffffffff.  A segment longer than rpp_order_chain_stage_rows()
+ * is chained in global memory, in d_perm itself:
+ * rpp_order_chain_workspace_bytes is 0 for every size.
+ */
+uint64_t rpp_order_chain_workspace_bytes(uint64_t total_entries);
+int rpp_order_chain_batch(const uint64_t* d_bits, uint32_t n_elems, const uint32_t* d_from_ids,
+                          const uint32_t* d_to_ids, const uint32_t* d_seg_start, uint32_t n_segments, uint32_t* d_perm,
+                          void* stream);
+
+/* The same on the host (host memory), written as the reference's sequential
+ * loops: one node's split, one segment's chain, and the whole order of `index`
+ * (n_index ids, any order, no id twice) into out[n_index]; stats may be NULL. */
+int rpp_order_host_split(const uint64_t* bits, uint32_t n_elems, const uint32_t* index, uint32_t m,
+                         uint32_t max_children, uint32_t max_distance, uint32_t* child, uint32_t* nchildren);
+int rpp_order_host_chain(const uint64_t* bits, uint32_t n_elems, const uint32_t* from_ids, const uint32_t* to_ids,
+                         uint32_t count, uint32_t* perm);
+int rpp_order_host_nilsimsa(const uint64_t* bits, const uint64_t* sizes, const uint32_t* rank, uint32_t n_elems,
+                            const uint32_t* index, uint32_t n_index, uint32_t max_children,
+                            uint32_t max_cluster_size, uint32_t* out, rpp_order_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif
