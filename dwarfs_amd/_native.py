@@ -22,6 +22,7 @@ RPP_OUTPUT_TOO_SMALL = -4
 RPP_HIP_ERROR = -5
 RPP_INTERNAL_ERROR = -6
 RPP_CHECKSUM_MISMATCH = -7
+RPP_CORRUPT_INPUT = -8
 
 RPP_DECODE_AUTO = 0
 RPP_DECODE_FUSED = 1
@@ -39,6 +40,7 @@ STATUS_NAMES = {
     RPP_HIP_ERROR: "HIP_ERROR",
     RPP_INTERNAL_ERROR: "INTERNAL_ERROR",
     RPP_CHECKSUM_MISMATCH: "CHECKSUM_MISMATCH",
+    RPP_CORRUPT_INPUT: "CORRUPT_INPUT",
 }
 
 # Every symbol declared in include/ricepp_amd.h.
@@ -127,6 +129,16 @@ EXPORTED_SYMBOLS = (
     "rpp_order_host_split",
     "rpp_order_host_chain",
     "rpp_order_host_nilsimsa",
+    "rpp_lz4_bound",
+    "rpp_lz4_chunk_bytes",
+    "rpp_lz4_step_positions",
+    "rpp_lz4_frame_header",
+    "rpp_lz4_parse_frame",
+    "rpp_lz4_decode_batch",
+    "rpp_lz4_encode_workspace_bytes",
+    "rpp_lz4_encode_batch",
+    "rpp_lz4_host_decode",
+    "rpp_lz4_host_encode",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -442,6 +454,25 @@ def lib() -> C.CDLL:
         L.rpp_order_host_chain.restype = C.c_int
         L.rpp_order_host_nilsimsa.argtypes = [P, P, P, U32, P, U32, U32, U32, P, C.POINTER(RppOrderStats)]
         L.rpp_order_host_nilsimsa.restype = C.c_int
+        L.rpp_lz4_bound.argtypes = [U64]
+        L.rpp_lz4_bound.restype = U64
+        for name in ("rpp_lz4_chunk_bytes", "rpp_lz4_step_positions"):
+            getattr(L, name).argtypes = []
+            getattr(L, name).restype = U32
+        L.rpp_lz4_frame_header.argtypes = [U32, P]
+        L.rpp_lz4_frame_header.restype = C.c_size_t
+        L.rpp_lz4_parse_frame.argtypes = [P, C.c_size_t, C.POINTER(U32)]
+        L.rpp_lz4_parse_frame.restype = C.c_long
+        L.rpp_lz4_decode_batch.argtypes = [P, P, P, U32, P, P, P, P, P]
+        L.rpp_lz4_decode_batch.restype = C.c_int
+        L.rpp_lz4_encode_workspace_bytes.argtypes = [U64, U32]
+        L.rpp_lz4_encode_workspace_bytes.restype = U64
+        L.rpp_lz4_encode_batch.argtypes = [P, P, P, U32, P, P, P, P, P, U64, P, U64, P]
+        L.rpp_lz4_encode_batch.restype = C.c_int
+        L.rpp_lz4_host_decode.argtypes = [P, U64, P, U64]
+        L.rpp_lz4_host_decode.restype = C.c_int
+        L.rpp_lz4_host_encode.argtypes = [P, U64, P, U64, C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_lz4_host_encode.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

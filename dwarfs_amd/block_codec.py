@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import lz4 as Z
 from . import section as S
 from .codec import CodecConfig, _check, _raise_status, decode_batch, encode_batch
 
@@ -270,14 +271,32 @@ def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[by
         if int(status.abs().sum().item()) != 0:
             raise RuntimeError(S.INTEGRITY_ERROR)
     decs, groups = [], {}
+    out: List[Optional[bytes]] = [None] * len(secs)
+    lz4_secs = []
     for i, (at, h) in enumerate(secs):
+        if h.type == S.SECTION_TYPE_BLOCK and h.compression == Z.COMPRESSION_TYPE_NONE:
+            out[i] = image[at + S.HEADER_BYTES:at + S.HEADER_BYTES + int(h.length)]  # stored as it is
+            decs.append(None)
+            continue
+        if h.type == S.SECTION_TYPE_BLOCK and h.compression in (Z.COMPRESSION_TYPE_LZ4, Z.COMPRESSION_TYPE_LZ4HC):
+            lz4_secs.append((i, at + S.HEADER_BYTES, int(h.length)))
+            decs.append(None)
+            continue
         if h.type != S.SECTION_TYPE_BLOCK or h.compression != COMPRESSION_TYPE_RICEPP:
             raise RuntimeError(f"section {h.number}: not a ricepp block (type {h.type}, compression {h.compression})")
         dec =RiceppBlockDecompressor(image[at + S.HEADER_BYTES:at + S.HEADER_BYTES + min(int(h.length), 64)], dev)
         hdr_len = min(int(h.length), 64) - len(dec.data)
         decs.append((dec, at + S.HEADER_BYTES + hdr_len, int(h.length) - hdr_len))
         groups.setdefault(dec.config, []).append(i)
-    out: List[Optional[bytes]] = [None] * len(secs)
+    if lz4_secs:  # LZ4 and LZ4HC decode alike: one launch, straight from the image on the device
+        sizes = [Z.parse_frame(image[at:at + length])[0] for _, at, length in lz4_secs]
+        plain, offs, st = Z.decode_batch(d_image, [at + Z.FRAME_BYTES for _, at, _ in lz4_secs],
+                                         [length - Z.FRAME_BYTES for _, _, length in lz4_secs], sizes)
+        torch.cuda.current_stream().synchronize()
+        host = plain.cpu().numpy()
+        for (i, _, _), o, n, s in zip(lz4_secs, offs, sizes, st.cpu().numpy()):
+            Z.raise_decode_status(int(s))
+            out[i] = host[o:o + n].tobytes()
     for cfg, idx in groups.items():
         ns = [decs[i][0].uncompressed_size() // 2 for i in idx]
         samples, st = decode_batch(cfg, d_image, [decs[i][1] for i in idx], [decs[i][2] for i in idx], ns)
@@ -292,9 +311,40 @@ def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[by
     return out  # type: ignore[return-value]
 
 
-def block_compressor(spec: str, device="cuda") -> RiceppBlockCompressor:
-    """``block_compressor(spec)`` for ``ricepp[:block_size=N]`` (src/compressor_registry.cpp:50-59)."""
+class NullBlockCompressor:
+    """``null_block_compressor`` (src/compression/null.cpp): compression type NONE, the bytes as they are."""
+
+    def clone(self) -> "NullBlockCompressor":
+        return NullBlockCompressor()
+
+    def type(self) -> int:
+        return Z.COMPRESSION_TYPE_NONE
+
+    def describe(self) -> str:
+        return "null"
+
+    def metadata_requirements(self) -> str:
+        return ""
+
+    def compress(self, data: bytes, metadata: Optional[str] = None) -> bytes:
+        return bytes(data)
+
+    def compress_many(self, blocks: Sequence[bytes], metadata: Optional[str] = None) -> List[bytes]:
+        return [bytes(b) for b in blocks]
+
+
+def block_compressor(spec: str, device="cuda"):
+    """``block_compressor(spec)`` for ``ricepp[:block_size=N]``, ``lz4``, ``lz4hc[:level=N]`` and ``null``
+    (src/compressor_registry.cpp:50-59)."""
     name, _, opts = spec.partition(":")
+    if name in ("lz4", "lz4hc", "null"):
+        level = 9 if name == "lz4hc" else None  # lz4.cpp's default level
+        for kv in filter(None, opts.split(",")):
+            k, eq, v = kv.partition("=")
+            if name != "lz4hc" or k != "level" or not eq or not v.isdigit() or int(v) > 12:
+                raise RuntimeError(f"invalid option(s) for {name}: {kv}")
+            level = int(v)
+        return NullBlockCompressor() if name == "null" else Z.Lz4BlockCompressor(level, device)
     if name != "ricepp":
         raise RuntimeError(f"unknown compression: {name}")
     bs = 128

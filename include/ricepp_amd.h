@@ -907,6 +907,90 @@ int rpp_order_host_nilsimsa(const uint64_t* bits, const uint64_t* sizes, const u
                             const uint32_t* index, uint32_t n_index, uint32_t max_children,
                             uint32_t max_cluster_size, uint32_t* out, rpp_order_stats* stats);
 
+/*
+ * lz4: the LZ4 block codec (src/compression/lz4.cpp), compression types LZ4 = 3
+ * and LZ4HC = 4 (include/dwarfs/compression.h:34-42), which decode alike.
+ *
+ *   payload   uint32 little-endian uncompressed size (rpp_lz4_frame_header /
+ *             rpp_lz4_parse_frame, lz4.cpp:88-106,127-169), then one LZ4 block
+ *             (the block format, not the frame format).
+ *   block     sequences: a token (high nibble literal length, low nibble match
+ *             length - 4; a nibble of 15 is followed by bytes that are added,
+ *             up to and including the first below 255), the literals, a 2-byte
+ *             little-endian offset 1..65535, the match length's bytes.  The
+ *             last sequence ends after its literals.  A match may overlap its
+ *             destination (offset < length: a repeated pattern).
+ *   decode    one wave per stream.  RPP_CORRUPT_INPUT when a token, an
+ *             extension byte, a literal or an offset would be read at or past
+ *             the stream's end; when a copy would pass the stated uncompressed
+ *             size; when an offset is 0 or reaches before the output's start;
+ *             when the stream ends before exactly the stated size has been
+ *             produced.  The last is stricter than the reference, which accepts
+ *             a short stream silently (lz4.cpp:143-152); a valid image never
+ *             holds one.  Nothing outside [out, out + size) is written and
+ *             nothing outside the stream is read, whatever the bytes are; what
+ *             the sequences before the failing one produced stays written.  The
+ *             end-of-block rules that LZ4_decompress_safe enforces are not
+ *             checked.
+ *   encode    deterministic, without atomics: chunks of rpp_lz4_chunk_bytes(),
+ *             searched in steps of rpp_lz4_step_positions() positions (lookups
+ *             of a step before its inserts), greedy, emitted as ONE block whose
+ *             literal runs span chunk boundaries; the complete definition is in
+ *             dwarfs_amd/csrc/lz4_host.cpp.  The last 5 bytes are literals, the
+ *             last match starts at least 12 bytes before the end, a block below
+ *             13 bytes is one literal run.  Not liblz4's bytes; any LZ4 decoder
+ *             reads them.  Blocks hold at most RPP_LZ4_MAX_BLOCK bytes (-S 30;
+ *             LZ4_compress_default takes an int): a longer one gets
+ *             RPP_INVALID_ARGUMENT in its status.
+ *
+ * The *_batch calls take device pointers and are asynchronous on `stream`.
+ */
+#define RPP_CORRUPT_INPUT (-8)
+#define RPP_LZ4_MAX_BLOCK (UINT64_C(1) << 30)
+
+/* Worst-case encoded bytes of an n-byte block: LZ4_compressBound's n + n / 255 + 16. */
+uint64_t rpp_lz4_bound(uint64_t n);
+/* The encoder's chunk size and the positions of one search step. */
+uint32_t rpp_lz4_chunk_bytes(void);
+uint32_t rpp_lz4_step_positions(void);
+
+/* Writes the 4-byte size prefix to out and returns 4. */
+size_t rpp_lz4_frame_header(uint32_t uncompressed_bytes, uint8_t* out);
+/* Returns 4, the LZ4 block's offset in the payload; RPP_TRUNCATED_INPUT for a payload below 4 bytes. */
+long rpp_lz4_parse_frame(const uint8_t* data, size_t size, uint32_t* uncompressed_bytes);
+
+/*
+ * Decodes nblocks LZ4 blocks: stream b is d_in[d_in_offsets[b] .. + d_in_bytes[b])
+ * (any alignment) and produces exactly d_out_bytes[b] bytes at d_out +
+ * d_out_offsets[b]; d_status[b] is RPP_OK or RPP_CORRUPT_INPUT.
+ */
+int rpp_lz4_decode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                         uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets,
+                         const uint64_t* d_out_bytes, int32_t* d_status, void* stream);
+
+/*
+ * Encodes nblocks blocks: block b is d_in[d_in_offsets[b] .. + d_in_bytes[b]) and
+ * its LZ4 block goes to d_out + d_out_offsets[b], a region of rpp_lz4_bound(n)
+ * bytes; d_out_bytes[b] is its size, d_flags[b] is 1 when 4 + size >= n (the
+ * writer's bad_compression_ratio_error: store the block as NONE) and else 0.  The
+ * caller owns the 16-aligned workspace of rpp_lz4_encode_workspace_bytes(
+ * total_bytes, nblocks) bytes, total_bytes >= the sum of d_in_bytes; if the device
+ * finds the sum larger, every status is RPP_INVALID_ARGUMENT and nothing is
+ * encoded.  No initialisation of the workspace is needed.
+ */
+uint64_t rpp_lz4_encode_workspace_bytes(uint64_t total_bytes, uint32_t nblocks);
+int rpp_lz4_encode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                         uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets, uint64_t* d_out_bytes,
+                         uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                         uint64_t workspace_bytes, void* stream);
+
+/* The two kernels' contracts as sequential host code (host memory): the CPU path
+ * and the yardstick.  rpp_lz4_host_encode writes exactly the kernel's bytes;
+ * capacity must be at least rpp_lz4_bound(n), else RPP_OUTPUT_TOO_SMALL. */
+int rpp_lz4_host_decode(const uint8_t* in, uint64_t in_bytes, uint8_t* out, uint64_t out_bytes);
+int rpp_lz4_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
+                        uint32_t* bad_ratio);
+
 #ifdef __cplusplus
 }
 #endif
