@@ -3,8 +3,13 @@
 // and flac_block_decompressor (src/compression/flac.cpp:215-403, :405-489;
 // the reference runs libFLAC++ on the CPU, one block per call).
 //
-// Parity is unpinned: libFLAC is absent here and the reference holds no FLAC
-// fixture.  The decoder accepts every frame kind RFC 9639 defines (constant,
+// Decode is pinned to libFLAC 1.3.3 by the three streams of RFC 9639
+// Appendix D and their MD5s (tests/golden/flac_rfc9639.json), and to the format
+// by frames written field by field (tests/flac_build.py, tests/flac_cases.py)
+// that an independent RFC 9639 reader (tests/flac_ref.py) and the CPU
+// restatement decode alike; the encoder is pinned to the format by that
+// reader, not bit-for-bit to libFLAC's encoder choices (the reference holds no
+// FLAC fixture).  The decoder accepts every frame kind RFC 9639 defines (constant,
 // verbatim, fixed and LPC subframes, wasted bits, both Rice methods, escape
 // partitions, the four channel assignments, any block size code), so it reads
 // libFLAC's streams; the encoder writes constant, verbatim, fixed and LPC
