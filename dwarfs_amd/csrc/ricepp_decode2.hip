@@ -8,7 +8,7 @@
 // they are split apart here:
 //
 //   1. where each sub-block starts: sub-block k+1 begins where the n-th code
-//      of sub-block k ends.  rpp_parse_kernel (ricepp_kernels.hip) finds the
+//      of sub-block k ends.  rpp_parse_kernel (ricepp_parse.hip) finds the
 //      starts, one wave per stream, with the exact table-driven parse and no
 //      value work, and writes them to sb_pos.
 //   2. the running value `last`: a sub-block's samples are its entry value
@@ -39,6 +39,7 @@
 
 #include "ricepp_amd.h"
 #include "ricepp_internal.h"
+#include "ricepp_wave.h"
 
 namespace {
 
@@ -231,28 +232,6 @@ struct ExtractParams {
   const uint32_t* stage_sel;
 };
 
-// pixel traits (ricepp/ricepp_cpuspecific_traits.h:63-75)
-__device__ __forceinline__ uint32_t px_read(uint32_t v, uint32_t be, uint32_t ulsb) {
-  v &= 0xFFFFu;
-  if (be) v = ((v >> 8) | (v << 8)) & 0xFFFFu;
-  return v >> ulsb;
-}
-__device__ __forceinline__ uint32_t px_write(uint32_t v, uint32_t be, uint32_t ulsb) {
-  v = (v << ulsb) & 0xFFFFu;
-  return be ? (((v >> 8) | (v << 8)) & 0xFFFFu) : v;
-}
-
-// stream word w (from the 4-aligned base), zero past the stream's last byte
-// (bitstream_reader.h:165-166 zero-pads the last packet)
-__device__ __forceinline__ uint32_t stream_word(const uint8_t* in, uint32_t nbytes, uint32_t w) {
-  const uint32_t byte0 = w * 4u;
-  if (byte0 >= nbytes) return 0u;
-  if (nbytes - byte0 >= 4) return *reinterpret_cast<const uint32_t*>(in + byte0);
-  uint32_t v = 0;
-  for (uint32_t k = 0; k < nbytes - byte0; ++k) v |= (uint32_t)in[byte0 + k] << (8 * k);
-  return v;
-}
-
 // scan element (reset?, value): bit 16 = a raw sub-block reset the value
 constexpr uint32_t kSet = 1u << 16;
 __device__ __forceinline__ uint32_t combine(uint32_t a, uint32_t b) {
@@ -264,24 +243,6 @@ __device__ __forceinline__ uint32_t combine(uint32_t a, uint32_t b) {
 constexpr uint64_t kFlagAgg = 1ull << 62, kFlagIncl = 2ull << 62;
 __device__ __forceinline__ uint64_t pack_state(uint32_t c0, uint32_t c1, uint64_t flag) {
   return flag | (uint64_t)(c0 & 0x1FFFFu) | ((uint64_t)(c1 & 0x1FFFFu) << 17);
-}
-
-// Asynchronous global -> LDS copy (global_load_lds_dword): lane l's 4 bytes
-// land at LDS byte address m0 + 4 l; retired by s_waitcnt vmcnt(0).
-__device__ __forceinline__ void glds4(const void* gsrc, uint32_t m0) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(m0) : "memory");
-}
-
-__device__ __forceinline__ uint32_t readlane(uint32_t v, int l) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-
-__device__ __forceinline__ uint32_t ffbl(uint32_t x) {
-  uint32_t r;
-  asm("v_ffbl_b32 %0, %1" : "=v"(r) : "v"(x));
-  return r;
 }
 
 // Bits of the stream for the general path: LDS tile when staged, else global.
@@ -344,18 +305,6 @@ __device__ uint32_t decode_general(const Reader& rd, uint32_t pos, uint32_t n, u
     if (STORE) dst[i * stride] = (uint16_t)px_write(acc, be, ulsb);
   }
   return acc & 0xFFFFu;
-}
-
-// Pixel write of two packed values (low, high), optional unused-LSB shift.
-template <bool SH>
-__device__ __forceinline__ uint32_t px_write2(uint32_t v, uint32_t sel, uint32_t ulsb) {
-  if (SH) {
-    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-    us2 x = __builtin_bit_cast(us2, v);
-    x = x << (us2)(unsigned short)ulsb;
-    v = __builtin_bit_cast(uint32_t, x);
-  }
-  return __builtin_amdgcn_perm(v, v, sel);
 }
 
 // BS: the block size of the fast lanes' unrolled decode (16..128); BS = 0 is
@@ -666,7 +615,7 @@ __global__ __launch_bounds__(kTile, STAGE == kStageWords ? 2 : 3) void rpp_extra
 // ===========================================================================
 // Segmented decode of long streams: units, stitch, positions, ragged tail
 // (the scheme: ricepp_internal.h; the parse of the units: rpp_parse_kernel
-// with SEG = true in ricepp_kernels.hip).
+// with SEG = true in ricepp_parse.hip).
 // ===========================================================================
 using rpp_internal::kSegNone;
 using rpp_internal::kSegOvr;

@@ -1,4 +1,6 @@
-// ricepp_frame.cpp -- DwarFS ricepp block framing (host side of the C ABI).
+// ricepp_frame.cpp -- the host-only entry points of the C ABI: the DwarFS
+// ricepp block framing, and the version, configuration check and worst-case
+// size (at the head of the extern "C" block).
 //
 // A DwarFS ricepp block is
 //   varint(uncompressed bytes)                 (src/varint.cpp:39-51, LEB128)
@@ -111,6 +113,24 @@ bool skip(reader& r, uint8_t t, int depth) {
 }  // namespace
 
 extern "C" {
+
+uint32_t rpp_abi_version(void) { return 1; }
+
+int rpp_check_config(const rpp_config* c) {
+  if (!c) return RPP_INVALID_ARGUMENT;
+  if (c->block_size == 0 || c->block_size > 512) return RPP_UNSUPPORTED_CONFIG;
+  if (c->component_stream_count != 1 && c->component_stream_count != 2) return RPP_UNSUPPORTED_CONFIG;
+  if (c->unused_lsb_count >= 16) return RPP_UNSUPPORTED_CONFIG;
+  return RPP_OK;
+}
+
+uint64_t rpp_worst_case_bytes(const rpp_config* c, uint64_t n) {
+  if (rpp_check_config(c) != RPP_OK) return 0;
+  const uint64_t cs = c->component_stream_count, bs = c->block_size;
+  const uint64_t per = n / cs;
+  const uint64_t num = 16 + 4 * ((per + bs - 1) / bs) + 16 * per;
+  return (num * cs + 7) / 8;
+}
 
 size_t rpp_frame_header(const rpp_frame* f, uint8_t* out) {
   size_t n = put_varint(out, f->uncompressed_bytes);

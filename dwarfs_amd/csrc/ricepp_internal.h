@@ -113,6 +113,27 @@ int launch_decode_fused(const rpp_config* cfg, const uint8_t* d_in, const uint64
                         const uint64_t* d_n_samples, int32_t* d_status, hipStream_t stream, bool only_fallback = false,
                         const uint64_t* d_units = nullptr, uint32_t waves = 0, bool rows = false);
 
+// rpp_decode_rows_kernel over a whole batch of bs 16 / 32 (the rows branch of
+// launch_decode_fused): streams it does not take are left with status
+// kSegFallback.  A launch error stays pending for the caller's
+// hipGetLastError.
+int launch_decode_rows(const rpp_config* cfg, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                       const uint64_t* d_in_bytes, uint32_t nblocks, uint16_t* d_out, const uint64_t* d_out_offsets,
+                       const uint64_t* d_n_samples, int32_t* d_status, hipStream_t stream);
+
+// Raises the dynamic LDS limit of every kernel in a launcher's table to
+// `bytes`.  Called once per table, as the initialiser of a function-local
+// static that keeps the result.
+template <typename K, size_t N>
+hipError_t set_max_dynamic_lds(K* const (&kernels)[N], size_t bytes) {
+  for (K* k : kernels) {
+    const hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // rpp_parse_kernel over units (SegView): the units of split streams, into
 // their position and overshoot lists (single-unit streams are left to the
 // fused kernel).

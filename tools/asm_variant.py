@@ -1,5 +1,5 @@
 """Diagnostic (DESIGN.md §4 "64-bit shifts and the last VGPR"): builds libricepp_amd_<name>.so
-from the RPP_DIAG_VALU_ANY build of ricepp_kernels.hip with its bs 128 cs 2
+from the RPP_DIAG_VALU_ANY build of ricepp_encode.hip with its bs 128 cs 2
 encode kernel's emission branches edited in the gfx950 assembly, to test
 what the fault depends on.  Edits (before each `s_cbranch_vccz` that follows
 the emission's `v_cmp_lt_u32 vcc, 32, vN`):
@@ -35,7 +35,7 @@ ROOT = Path(__file__).resolve().parent.parent
 KERNEL = "_ZN12_GLOBAL__N_117rpp_encode_kernelILj16ELj8ELj2ELb0EEEvNS_9EncParamsE"
 edit = sys.argv[1]
 tmp = Path(tempfile.mkdtemp(prefix="asmvar-"))
-src = ROOT / "dwarfs_amd/csrc/ricepp_kernels.hip"
+src = ROOT / "dwarfs_amd/csrc/ricepp_encode.hip"
 base = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++20", "--offload-arch=gfx950", "-fPIC", "-I", str(ROOT / "include"),
         "-DRPP_DIAG_VALU_ANY", "-c", str(src), "-o", str(tmp / "rk.o")]
 out = subprocess.run(base + ["-###"], capture_output=True, text=True).stderr
@@ -143,7 +143,7 @@ subprocess.run(host, check=True)
 # 4. the library: this object + the others as build_native compiles them
 objs = [str(tmp / "rk.o")]
 flags = ["-O3", "-std=c++20", "--offload-arch=gfx950", "-fPIC", "-I", str(ROOT / "include")]
-for s in ["ricepp_decode2.hip", "fits_lsb.hip", "batch_image.hip", "pcm_transform.hip", "flac_kernels.hip",
+for s in ["ricepp_decode_fused.hip", "ricepp_decode_rows.hip", "ricepp_parse.hip", "ricepp_decode2.hip", "fits_lsb.hip", "batch_image.hip", "pcm_transform.hip", "flac_kernels.hip",
           "ricepp_frame.cpp", "ricepp_facade.cpp"]:
     o = tmp / (s + ".o")
     subprocess.run(["/opt/rocm/bin/hipcc", *flags, "-c", str(ROOT / "dwarfs_amd/csrc" / s), "-o", str(o)], check=True)

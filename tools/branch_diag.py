@@ -2,7 +2,7 @@
 benchmark-generator blocks at bs 128 cs 2 with the library named by
 RICEPP_AMD_LIB (a tools/variant.sh build), counts the streams that differ from
 the oracle, and -- for a -DRPP_DIAG_BRANCH_CHECK build -- reads the emission
-branch counters (ricepp_kernels.hip branch_diag).  One JSON line per repeat.
+branch counters (ricepp_decode_fused.hip branch_diag).  One JSON line per repeat.
 Usage: RICEPP_AMD_LIB=... python tools/branch_diag.py <label> [repeats] [nblocks]"""
 import ctypes as C
 import json

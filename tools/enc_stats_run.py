@@ -15,16 +15,16 @@ from bench import make_poisson_blocks  # noqa: E402
 from dwarfs_amd import _native, codec, parallel  # noqa: E402
 
 L = _native.lib()
-L.rpp_stats_fetch.argtypes = [C.c_void_p, C.c_int]
+L.rpp_enc_stats_fetch.argtypes = [C.c_void_p, C.c_int]
 n = 32768
 x = make_poisson_blocks(nblocks, n, 1000.0, 42, torch.device("cuda:0"))
 pipe = parallel.ShardPipeline(codec.CodecConfig(128, 1, "big", 0), x, np.arange(nblocks) * n, np.full(nblocks, n))
 torch.cuda.synchronize()
 st = np.zeros(16, np.uint64)
-L.rpp_stats_fetch(st.ctypes.data, 1)
+L.rpp_enc_stats_fetch(st.ctypes.data, 1)
 pipe.encode()
 torch.cuda.synchronize()
-L.rpp_stats_fetch(st.ctypes.data, 1)
+L.rpp_enc_stats_fetch(st.ctypes.data, 1)
 it = float(st[0])
 print(f"encode nblocks {nblocks}: steps {int(it)}")
 for i in range(1, 16):
