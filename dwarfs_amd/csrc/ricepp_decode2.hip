@@ -934,6 +934,7 @@ __global__ void rpp_seg_tail_kernel(SegArgs a) {
   int32_t st = RPP_OK;
   if (a.sv.sflags[b] & kSfListFull) {
     st = kSegFallback;
+    atomicAdd(&g_seg_diag[3], 1ull);
   } else if (T < need) {
     st = (a.sv.sflags[b] & kSfPastRegion) ? kSegFallback : RPP_TRUNCATED_INPUT;
     if (st == kSegFallback) atomicAdd(&g_seg_diag[3], 1ull);

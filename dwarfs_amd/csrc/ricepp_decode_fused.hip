@@ -614,6 +614,9 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
       // ---- codes [xdone, m) -> zig-zag deltas (decode.h:66-69) -> values,
       //      2 per lane (m even or m == n) ----
       uint32_t acc = comp ? last1 : last0, start = P4, xdone = 0;  // start: first bit of code xdone's unary run
+      // a code left over by an odd count when the parse moves to the next window: its remainder, read while
+      // the ring still holds it (the run that follows may be longer than the ring keeps)
+      uint32_t held_i = 0xFFFFFFFFu, held_r = 0;
       auto extract = [&](uint32_t m) {
         for (; xdone < m; xdone += 2 * kWave) {
           const uint32_t i0 = xdone + 2 * lane;
@@ -621,7 +624,7 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
           const uint2 tt = *reinterpret_cast<const uint2*>(&list[min(i0, kListDump - 2)]);
           const uint32_t t0 = tt.x, t1 = ok1 ? tt.y : t0;
           const uint32_t st0 = dpp_keep<kDppWaveShr1>(start, t1 + k);  // end of code i0 - 1
-          const uint32_t r0 = peek32(t0 + 1) & fmask, r1 = peek32(t1 + 1) & fmask;
+          const uint32_t r0 = i0 == held_i ? held_r : peek32(t0 + 1) & fmask, r1 = peek32(t1 + 1) & fmask;
           const uint32_t df0 = ((t0 - st0) << fs) | r0, df1 = ((t1 - t0 - k) << fs) | r1;
           const uint32_t d0 = ok0 ? (df0 >> 1) ^ (0u - (df0 & 1u)) : 0u;
           const uint32_t d1 = ok1 ? (df1 >> 1) ^ (0u - (df1 & 1u)) : 0u;
@@ -711,6 +714,11 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
         if ((done & ~1u) > xdone) {
           lds_fence();
           extract(done & ~1u);
+        }
+        if ((done & 1u) && held_i != done - 1) {
+          lds_fence();
+          held_i = done - 1;
+          held_r = __builtin_amdgcn_readfirstlane(peek32(list[held_i] + 1)) & fmask;
         }
         s0 = wave_last(xexit);
         q0 += kWinBits;
