@@ -139,6 +139,11 @@ EXPORTED_SYMBOLS = (
     "rpp_lz4_encode_batch",
     "rpp_lz4_host_decode",
     "rpp_lz4_host_encode",
+    "rpp_zstd_frame_info",
+    "rpp_zstd_count_blocks",
+    "rpp_zstd_decode_workspace_bytes",
+    "rpp_zstd_decode_batch",
+    "rpp_zstd_host_decode",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -473,6 +478,16 @@ def lib() -> C.CDLL:
         L.rpp_lz4_host_decode.restype = C.c_int
         L.rpp_lz4_host_encode.argtypes = [P, U64, P, U64, C.POINTER(U64), C.POINTER(U32)]
         L.rpp_lz4_host_encode.restype = C.c_int
+        L.rpp_zstd_frame_info.argtypes = [P, C.c_size_t, C.POINTER(U64), C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_zstd_frame_info.restype = C.c_long
+        L.rpp_zstd_count_blocks.argtypes = [P, C.c_size_t]
+        L.rpp_zstd_count_blocks.restype = C.c_long
+        L.rpp_zstd_decode_workspace_bytes.argtypes = [U64, U32]
+        L.rpp_zstd_decode_workspace_bytes.restype = U64
+        L.rpp_zstd_decode_batch.argtypes = [P, P, P, U32, P, P, P, P, U32, P, U64, P]
+        L.rpp_zstd_decode_batch.restype = C.c_int
+        L.rpp_zstd_host_decode.argtypes = [P, U64, P, U64]
+        L.rpp_zstd_host_decode.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

@@ -30,6 +30,7 @@ import torch
 from . import _native as N
 from . import lz4 as Z
 from . import section as S
+from . import zstd as ZS
 from .codec import CodecConfig, _check, _raise_status, decode_batch, encode_batch
 
 COMPRESSION_TYPE_RICEPP = 7  # include/dwarfs/compression.h
@@ -247,7 +248,9 @@ def compress_many_sections(blocks: Sequence[bytes], metadata: Optional[str], fir
 
 
 def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[bytes]:
-    """Decodes the ricepp BLOCK sections of an image fragment (as ``compress_many_sections`` writes them).
+    """Decodes the BLOCK sections of an image fragment: ricepp (as ``compress_many_sections`` writes them), LZ4
+    and LZ4HC, NONE, and ZSTD as a stock ``mkdwarfs`` writes them (one Zstandard frame per section; their block
+    counts come from the host copy).  Any other compression (lzma, brotli, flac) raises.
 
     The headers are walked on the host, the image goes to the device in one copy, and the integrity check
     (``verify`` 1: XXH3-64 as cached_block's check_fast, src/reader/internal/cached_block.cpp:58-67; 2: also
@@ -272,7 +275,7 @@ def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[by
             raise RuntimeError(S.INTEGRITY_ERROR)
     decs, groups = [], {}
     out: List[Optional[bytes]] = [None] * len(secs)
-    lz4_secs = []
+    lz4_secs, zstd_secs = [], []
     for i, (at, h) in enumerate(secs):
         if h.type == S.SECTION_TYPE_BLOCK and h.compression == Z.COMPRESSION_TYPE_NONE:
             out[i] = image[at + S.HEADER_BYTES:at + S.HEADER_BYTES + int(h.length)]  # stored as it is
@@ -282,8 +285,13 @@ def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[by
             lz4_secs.append((i, at + S.HEADER_BYTES, int(h.length)))
             decs.append(None)
             continue
+        if h.type == S.SECTION_TYPE_BLOCK and h.compression == ZS.COMPRESSION_TYPE_ZSTD:
+            zstd_secs.append((i, at + S.HEADER_BYTES, int(h.length)))
+            decs.append(None)
+            continue
         if h.type != S.SECTION_TYPE_BLOCK or h.compression != COMPRESSION_TYPE_RICEPP:
-            raise RuntimeError(f"section {h.number}: not a ricepp block (type {h.type}, compression {h.compression})")
+            raise RuntimeError(f"section {h.number}: not a ricepp, lz4, zstd or uncompressed block "
+                               f"(type {h.type}, compression {h.compression})")
         dec =RiceppBlockDecompressor(image[at + S.HEADER_BYTES:at + S.HEADER_BYTES + min(int(h.length), 64)], dev)
         hdr_len = min(int(h.length), 64) - len(dec.data)
         decs.append((dec, at + S.HEADER_BYTES + hdr_len, int(h.length) - hdr_len))
@@ -296,6 +304,19 @@ def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[by
         host = plain.cpu().numpy()
         for (i, _, _), o, n, s in zip(lz4_secs, offs, sizes, st.cpu().numpy()):
             Z.raise_decode_status(int(s))
+            out[i] = host[o:o + n].tobytes()
+    if zstd_secs:  # one batch, straight from the image on the device
+        frames = [ZS.ZstdBlockDecompressor(image[at:at + length], dev) for _, at, length in zstd_secs]
+        sizes = [f.uncompressed_size() for f in frames]
+        blocks = [ZS.count_blocks(f.data) for f in frames]
+        for b in blocks:
+            ZS.raise_decode_status(min(b, 0))
+        plain, offs, st = ZS.decode_batch(d_image, [at for _, at, _ in zstd_secs],
+                                          [length for _, _, length in zstd_secs], sizes, sum(blocks))
+        torch.cuda.current_stream().synchronize()
+        host = plain.cpu().numpy()
+        for (i, _, _), o, n, s in zip(zstd_secs, offs, sizes, st.cpu().numpy()):
+            ZS.raise_decode_status(int(s))
             out[i] = host[o:o + n].tobytes()
     for cfg, idx in groups.items():
         ns = [decs[i][0].uncompressed_size() // 2 for i in idx]

@@ -991,6 +991,75 @@ int rpp_lz4_host_decode(const uint8_t* in, uint64_t in_bytes, uint8_t* out, uint
 int rpp_lz4_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
                         uint32_t* bad_ratio);
 
+/*
+ * zstd: the Zstandard block decoder (src/compression/zstd.cpp:443-483),
+ * compression type ZSTD = 2 (include/dwarfs/compression.h:34-42).  No encoder.
+ *
+ *   payload   ONE Zstandard frame (RFC 8878), as ZSTD_compress2 writes it
+ *             (zstd.cpp:424-441): single-segment or with a Window_Descriptor,
+ *             any Frame_Content_Size width, no dictionary (a Dictionary_ID of 0
+ *             is accepted).  The reader takes the buffer size from the frame
+ *             header (rpp_zstd_frame_info) and states it to the decoder.
+ *   decode    three launches: index (one lane per frame: frame and block
+ *             headers, who supplies a Treeless tree or a Repeat table), entropy
+ *             (one wave per block: Huffman literals, 4 streams in 4 lanes, and
+ *             FSE sequences into records in the workspace), execute (one wave per
+ *             frame: repeat offsets, literal and match copies).  Raw, RLE and
+ *             Compressed blocks; Raw, RLE, Compressed and Treeless literals;
+ *             Predefined, RLE, FSE_Compressed and Repeat tables.  The complete
+ *             list of what is RPP_CORRUPT_INPUT is at the top of
+ *             dwarfs_amd/csrc/zstd_host.cpp; it includes three rules of the RFC
+ *             that libzstd 1.4.8 does not enforce (reserved mode bits, unused
+ *             sequence bits, an offset of 0 through the repeat rule), any byte
+ *             behind the frame, and a frame that does not produce exactly the
+ *             stated size.  A frame without Frame_Content_Size is decoded; the
+ *             stated size stands in.  The Content_Checksum's 4 bytes must be
+ *             there when flagged and are skipped, NOT verified (XXH64; every
+ *             section carries XXH3-64 already).  Nothing outside a frame's input
+ *             is read and nothing outside its output region is written, whatever
+ *             the bytes are; a refused frame's output region is unspecified.
+ *             Frames and contents hold less than 4 GiB each: a larger one gets
+ *             RPP_INVALID_ARGUMENT in its status.
+ *
+ * rpp_zstd_decode_batch takes device pointers and is asynchronous on `stream`.
+ */
+#define RPP_ZSTD_FLAG_SINGLE_SEGMENT 1u
+#define RPP_ZSTD_FLAG_CHECKSUM 2u
+#define RPP_ZSTD_FLAG_CONTENT_SIZE 4u
+
+/* Parses the frame header (host memory): its length, or RPP_CORRUPT_INPUT.  *content_size is 0 without
+ * RPP_ZSTD_FLAG_CONTENT_SIZE in *flags; *window is the content size for a single-segment frame.  Any of the
+ * three may be NULL. */
+long rpp_zstd_frame_info(const uint8_t* data, size_t size, uint64_t* content_size, uint64_t* window,
+                         uint32_t* flags);
+/* Walks the block headers of a frame (host memory): the number of blocks, or RPP_CORRUPT_INPUT when a header
+ * cannot be read, a block passes the end or has the Reserved type. */
+long rpp_zstd_count_blocks(const uint8_t* data, size_t size);
+
+/*
+ * Decodes nframes frames: frame b is d_in[d_in_offsets[b] .. + d_in_bytes[b]) (any
+ * alignment, no padding needed) and produces exactly d_out_bytes[b] bytes at
+ * d_out + d_out_offsets[b]; d_status[b] is RPP_OK, RPP_CORRUPT_INPUT, or
+ * RPP_OUTPUT_TOO_SMALL for a frame that does not fit the workspace.  max_blocks
+ * is the caller's promise of the blocks of all frames together (the sum of
+ * rpp_zstd_count_blocks), and the 16-aligned workspace holds
+ * rpp_zstd_decode_workspace_bytes(total_out_bytes, max_blocks) bytes,
+ * total_out_bytes >= the sum of d_out_bytes (about 5 bytes per output byte).
+ * Slots are dealt out frame by frame: a frame with more blocks, or more output,
+ * than is left takes none, gets RPP_OUTPUT_TOO_SMALL, and nothing of it is
+ * decoded; the frames behind it go on.  max_blocks < nframes returns
+ * RPP_OUTPUT_TOO_SMALL at once; nframes == 0 returns RPP_OK at once.  No
+ * initialisation of the workspace is needed.
+ */
+uint64_t rpp_zstd_decode_workspace_bytes(uint64_t total_out_bytes, uint32_t max_blocks);
+int rpp_zstd_decode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                          uint32_t nframes, uint8_t* d_out, const uint64_t* d_out_offsets,
+                          const uint64_t* d_out_bytes, int32_t* d_status, uint32_t max_blocks, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream);
+
+/* The kernels' contract as sequential host code (host memory): the CPU path and the yardstick. */
+int rpp_zstd_host_decode(const uint8_t* in, uint64_t in_bytes, uint8_t* out, uint64_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif
