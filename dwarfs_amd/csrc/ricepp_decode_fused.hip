@@ -35,6 +35,12 @@
 #include "ricepp_stats.h"
 #include "ricepp_tables.h"
 
+// -DRPP_W16=0 builds the kernel without the 16-bit-segment instance of the
+// fast loop (below), for an A/B from one tree.
+#ifndef RPP_W16
+#define RPP_W16 1
+#endif
+
 #ifdef RPP_STATS
 __device__ unsigned long long g_dec_stats[16];
 #endif
@@ -43,6 +49,24 @@ namespace {
 
 // wave priority over the fast loop's parse chain (profiles/r02_prio_ab.jsonl)
 constexpr int kParsePrio = 1;
+
+// The narrow instance of the fs 5..7, bs 128 fast loop: 64 lane segments of
+// 16 bits.  A sub-block whose 128th terminator lies in these 1024 bits is
+// parsed with two table lookups per lane instead of three; one that is longer
+// is handed to the 24-bit instance.
+constexpr uint32_t kSeg16Bits = 16;
+constexpr uint32_t kWin16Bits = kWave * kSeg16Bits;
+// Sub-blocks in a row that the 24-bit instance must see fit in kWin16Bits
+// before the stream goes back to the narrow instance.  A change of instance
+// costs an unpipelined parse (about three sub-block times) each way, a
+// fitting sub-block in the 24-bit instance about an eighth of one more than
+// in the narrow one.  In Poisson(1000) data 0.26 % of the sub-blocks are long
+// and 90 % of them have no other within 16 sub-blocks,
+// so any small value serves there; 8 also keeps data whose sub-blocks lie
+// around the window's length (a long one in every few) from changing
+// instance at each of them: with a share p of long ones a return takes a run
+// of 8 fitting ones, (1 - p)^8 of the positions.
+constexpr uint32_t kW16Return = 8;
 
 // the table entry at byte offset off16 (16 * entry) from tb
 __device__ __forceinline__ uint4 tb_entry(const uint4* tb, uint32_t off16) {
@@ -77,6 +101,7 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
   const uint32_t selbe = be ? 0x02030001u : 0x03020100u;
   const uint32_t selpack = be ? 0x04050001u : 0x05040100u;  // v_perm(hi, lo): pack two samples (+ swap)
   const uint32_t lane24 = kSegBits * lane;
+  const uint32_t lane16 = kSeg16Bits * lane;
   if (!mine) return;  // no barrier below this point
 #ifdef RPP_STATS
   uint32_t stat_acc[16] = {0};
@@ -239,6 +264,9 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
   // the stream's output as a raw buffer (N * 2 < 2^28 bytes; stores past it are dropped)
   const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(out, (short)0, (int)(2 * N), 0x00020000);
   ScanRegs sreg;
+  // fs 5..7, bs 128: sub-blocks in a row seen to fit the narrow window
+  // (wave-uniform; the narrow instance runs while it is at kW16Return)
+  uint32_t fit_run = kW16Return;
 
   for (uint32_t s = 0; s < nsb && status == RPP_OK; ++s) {
     rebase();
@@ -253,21 +281,29 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
     // MT: terminators a lane segment can hold (codes of >= fs + 1 bits),
     // [LO, HI]: the fs range of this instance (fs 8..13: 32-bit segments)
     // TWO: bs 128, two codes per lane; else bs <= 64, one code per lane
-    auto fast = [&]<uint32_t MT, uint32_t LO, uint32_t HI, bool TWO>() {
+    // W16: the narrow instance (16-bit segments, two table bytes per lane,
+    // at most 3 terminators: codes of fs 5..7 are >= 6 bits, so a segment
+    // holds terminators at most at t, t + 6, t + 12)
+    auto fast = [&]<uint32_t MT, uint32_t LO, uint32_t HI, bool TWO, bool W16 = false>() {
       // fs >= 8: 32-bit lane segments (2048-bit windows), entry states by
       // jacobi rounds over 14 states; else 24-bit segments and 8-state maps
       constexpr bool W32 = LO >= 8;
-      constexpr uint32_t SB = W32 ? 32u : kSegBits;
+      static_assert(!W16 || (LO >= 5 && HI <= 7 && MT == 3 && TWO), "16-bit segments: fs 5..7, bs 128");
+      constexpr uint32_t SB = W32 ? 32u : W16 ? kSeg16Bits : kSegBits;
+      // the 24-bit instance that counts fitting sub-blocks for the return to
+      // the narrow one
+      constexpr bool kCountFit = RPP_W16 != 0 && !W16 && LO == 5 && HI == 7 && TWO;
       const uint32_t n = TWO ? 2 * kWave : bs;
       const uint4* const list4 = reinterpret_cast<const uint4*>(list);
       uint2* const list2 = reinterpret_cast<uint2*>(list);
       // this lane's 32 bits from bit q + SB lane (24-bit segments: the
       // segment and 8 more, where a terminator in it has its <= 7 remainder
-      // bits; 32-bit segments: the next 32 bits in xh)
+      // bits; 16-bit segments: the segment and 16 more; 32-bit segments: the
+      // next 32 bits in xh)
       // (window start word and bit offset are scalar; 24-bit segments: the
-      // lane's words lie within 50 words of the window start, inside the
-      // ring's mirror; 32-bit segments: the first word index is wrapped per
-      // lane, the next two are in the mirror)
+      // lane's words lie within 50 words of the window start (16-bit: within
+      // 33), inside the ring's mirror; 32-bit segments: the first word index
+      // is wrapped per lane, the next two are in the mirror)
       auto seg_bits = [&](uint32_t q, uint32_t& xh) {
         if constexpr (W32) {
           const uint32_t* w = ring + (((q >> 5) + lane) & kRingMask);
@@ -277,7 +313,7 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
         } else {
           // (vector addressing from q + lane24 alone: no scalar splitting of
           // q; word wi + 1 <= kRingWords lies in the ring's mirror)
-          const uint32_t x = q + lane24;
+          const uint32_t x = q + (W16 ? lane16 : lane24);
           const uint32_t* w = ring + ((x >> 5) & kRingMask);
           xh = 0u;
           return __builtin_amdgcn_alignbit(w[1], w[0], x);  // (shift x mod 32)
@@ -310,7 +346,7 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
         uint32_t tot2;  // lane 63's inclusive sums: the window's code count (low), the rider's total (high)
         if constexpr (!W32) {
           const Map8 M01 = comp8(Map8{e1.x, e1.y}, Map8{e0.x, e0.y});  // (also gives byte 2's entry state)
-          const Map8 M = comp8(Map8{e2.x, e2.y}, M01);
+          const Map8 M = W16 ? M01 : comp8(Map8{e2.x, e2.y}, M01);
           // state 4 at the window start: skip the header.  A selector
           // carries the state in byte 0 (the other bytes are 0xFF or copies
           // of byte 0), so each byte's next state comes out of its v_perm as
@@ -326,10 +362,11 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
             return __builtin_amdgcn_perm(X.hi, X.lo, 0xFFFFFF04u);
           };
           // terminator mask of the segment entered in state sel: byte 0 of
-          // a0, a1, a2 -> bytes 0, 1, 2
+          // a0, a1, a2 -> bytes 0, 1, 2 (16-bit segments: of a0, a1)
           auto term_mask = [&](uint32_t sel) {
             const uint32_t a0 = __builtin_amdgcn_perm(e0.w, e0.z, sel);
             const uint32_t a1 = __builtin_amdgcn_perm(e1.w, e1.z, __builtin_amdgcn_perm(e0.y, e0.x, sel));
+            if constexpr (W16) return __builtin_amdgcn_perm(a1, a0, 0x0C0C0400u);
             const uint32_t a2 = __builtin_amdgcn_perm(e2.w, e2.z, __builtin_amdgcn_perm(M01.hi, M01.lo, sel));
             return __builtin_amdgcn_perm(a2, __builtin_amdgcn_perm(a1, a0, 0x0C0C0400u), 0x0C040100u);
           };
@@ -365,7 +402,11 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
         const uint32_t base = cnt != 0 && excl < n ? excl : 256u;
         uint32_t abase = (uint32_t)((int)(SB * lane - 4u) + __mul24((int)base, -(int)k));
         asm volatile("" : "+v"(abase));  // computed once, not per pair
-        const uint32_t xr = xl >> 1;     // the remainder of a terminator at t is bits t+1 .. t+fs
+        // the remainder of a terminator at t is bits t+1 .. t+fs of xl: up
+        // to bit 23 + 7 = 30 with 24-bit segments, 15 + 7 = 22 with 16-bit
+        // ones (the segment's last terminator reaches into the next lane's
+        // bits, which xl's 32 hold)
+        const uint32_t xr = xl >> 1;
 #pragma unroll
         for (int j = MT - 1; j >= 0; --j) {
           // (32-bit segments: the remainder may reach into the next word)
@@ -446,7 +487,8 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
         const uint4* tb = tab + 256u * fs;
         e0 = tb_entry(tb, sdwa_byte16<0>(xl));
         e1 = tb_entry(tb, sdwa_byte16<1>(xl));
-        e2 = tb_entry(tb, sdwa_byte16<2>(xl));
+        if constexpr (!W16) e2 = tb_entry(tb, sdwa_byte16<2>(xl));
+        if constexpr (W16) e2 = make_uint4(0u, 0u, 0u, 0u);
         if constexpr (W32) e3 = tb_entry(tb, sdwa_byte16<3>(xl));
         if constexpr (!W32) e3 = make_uint4(0u, 0u, 0u, 0u);
       };
@@ -480,6 +522,11 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
       uint32_t xlB, xhB;  // the window of the sub-block at Pn
       uint32_t ok =
           parse(P, xl, xh, fs, e0, e1, e2, e3, Pn, xlB, xhB, 0u, unused_rider, [](uint32_t, uint32_t) {}) & header_ok(h);
+      // a sub-block that does not end in the narrow window: the 24-bit
+      // instance takes over (also below, at the loop's own parse)
+      if constexpr (W16) {
+        if (!ok) fit_run = 0;
+      }
       // the look-ahead bound when the window at Pn was read (ring_keep may
       // raise pn_limit afterwards; the window read earlier stays good only
       // below the bound of its time)
@@ -499,12 +546,21 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
         const uint32_t hB = __builtin_amdgcn_readfirstlane(xlB);
         RPP_TSTAMP(1);
         RPP_STAT(0, 1);
+        if constexpr (W16) RPP_STAT(3, 1);
         uint32_t d1A, sumA, incA;
         // Does the loop go on to the sub-block at Pn?  (Computed here, tested
         // with the parse's own result after it, so that sub-block s's values
         // still ride on that parse's scan; testing it first, as scalar
         // branches, measured 5 % slower: profiles/r04_decode_ab.jsonl.)
-        const uint32_t nxt = (uint32_t)(s + 1 < nsb_fast) & (uint32_t)(Pn <= pn_read_limit) & header_ok(hB);
+        uint32_t nxt = (uint32_t)(s + 1 < nsb_fast) & (uint32_t)(Pn <= pn_read_limit) & header_ok(hB);
+        // sub-block s is Pn - P bits: after kW16Return in a row that the
+        // narrow window holds, leave (like at a header of another class) for
+        // the narrow instance.  (A sub-block of up to kWin16Bits + fs bits
+        // would fit; the bound without fs is one scalar compare.)
+        if constexpr (kCountFit) {
+          fit_run = Pn - P <= kWin16Bits ? fit_run + 1 : 0u;
+          nxt &= (uint32_t)(fit_run < kW16Return);
+        }
         pn_read_limit = pn_limit;
         const uint32_t fsB = fs_of(hB);
         lookups(xlB, fsB, e0, e1, e2, e3);
@@ -515,6 +571,9 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
                    [&](uint32_t inc, uint32_t inc_last) { store(d1A, inc, inc_last, s); });
         ++s;
         P = Pn;
+        if constexpr (W16) {
+          if (!ok) fit_run = 0;
+        }
         if (!(ok & nxt)) {
           if (P > lim) status = RPP_TRUNCATED_INPUT;
           break;
@@ -542,6 +601,14 @@ __global__ __launch_bounds__(kWave* kDecMaxWaves) void rpp_decode_kernel(DecPara
       // (fs 1: the fs 1-4 instance, 12 terminators per segment; a stream
       // that mixes fs 1 and 2..4 sub-blocks stays in it)
       if (bs == 2 * kWave) {
+#if RPP_W16
+        if (h - 6u <= 2u && fit_run >= kW16Return) {
+          fast.template operator()<3, 5, 7, true, true>();
+          // (no progress: the first sub-block is too long for the narrow
+          // window, and fit_run is 0 now)
+          if (s == s0 && fit_run < kW16Return) continue;
+        } else
+#endif
         if (h - 6u <= 2u) fast.template operator()<4, 5, 7, true>();
         else if (h - 3u <= 2u) fast.template operator()<8, 2, 4, true>();
         else if (h - 9u <= 5u) fast.template operator()<4, 8, 13, true>();

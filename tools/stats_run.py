@@ -32,6 +32,7 @@ pipe.check(x)
 L.rpp_dec_stats_fetch(st.ctypes.data, 1)
 it = float(st[0])
 print(f"nblocks {nblocks} waves {waves or 'auto'}: fast iterations {int(it)}")
+print(f"of them in the 16-bit-segment instance (slot 3): {int(st[3])}")
 for i in range(1, 16):
-    if st[i]:
+    if st[i] and i != 3:
         print(f"slot {i:2d} cycles/iteration {st[i] / it:8.1f}")
