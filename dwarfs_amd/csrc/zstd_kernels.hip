@@ -11,8 +11,12 @@
 //            its sections start, which earlier block supplies its Huffman tree
 //            (Treeless) and each Repeat table, and where its literals and
 //            sequence records go in the workspace.  Slots are dealt out frame by
-//            frame; a frame that does not fit what the caller promised gets
-//            RPP_OUTPUT_TOO_SMALL and nothing of it is decoded.
+//            frame, to the valid frames first; one that does not fit what the
+//            caller promised gets RPP_OUTPUT_TOO_SMALL and nothing of it is
+//            decoded.  A frame whose walk fails at a block keeps the blocks
+//            before it, so that what they produce is written as the contract
+//            says, where slots are left behind the valid frames'; its status
+//            stays corrupt.
 //   entropy  one wave per block, kEntropyWaves per workgroup.  Entropy decoding
 //            needs no output byte of an earlier block, so every block of every
 //            frame runs at once.  Lane 0 builds the Huffman table (2^11 entries)
@@ -87,7 +91,8 @@ __device__ inline void wave_copy(uint8_t* d, const uint8_t* s, uint64_t n, uint3
 // ---------------------------------------------------------------------------
 // index
 // ---------------------------------------------------------------------------
-// Walks one frame; with `recs` it writes the first `cap` block records.  The frame's status.
+// Walks one frame; with `recs` it writes the first `cap` block records.  The frame's status; fr.nblocks counts
+// the blocks walked without fault, also where a later one fails.
 __device__ int32_t walk_frame(const uint8_t* in, uint64_t in_n, uint64_t out_n, uint32_t frame, FrameRec& fr,
                               BlockRec* recs, uint32_t cap) {
   if (in_n >> 32 || out_n >> 32) return RPP_INVALID_ARGUMENT;  // positions are kept in 32 bits
@@ -99,6 +104,7 @@ __device__ int32_t walk_frame(const uint8_t* in, uint64_t in_n, uint64_t out_n, 
   uint64_t at = h.bytes, lit_sum = 0, seq_sum = 0;
   uint32_t nb = 0, last_huf = kNone, last_tab[3] = {kNone, kNone, kNone};
   for (;;) {  // every turn passes at least the 3 bytes of a block header
+    fr.nblocks = nb;
     if (at + 3 > in_n) return RPP_CORRUPT_INPUT;
     const uint32_t hd = uint32_t(rd_le(in + at, 3)), kind = hd >> 1 & 3, size = hd >> 3;
     const uint64_t held = kind == kRle ? 1 : size;
@@ -151,8 +157,8 @@ __device__ int32_t walk_frame(const uint8_t* in, uint64_t in_n, uint64_t out_n, 
     at += 3 + held;
     if (hd & 1) break;
   }
+  fr.nblocks = nb;  // (all blocks are sound also where what follows them is not)
   if (at + ((h.flags & kFlagChecksum) ? 4 : 0) != in_n) return RPP_CORRUPT_INPUT;  // (the checksum is skipped)
-  fr.nblocks = nb;
   return RPP_OK;
 }
 
@@ -168,30 +174,38 @@ __global__ __launch_bounds__(kIndexThreads) void rpp_zstd_index_kernel(
   if (threadIdx.x == 0) {  // slots frame by frame: a frame that does not fit takes none
     uint32_t base = 0;
     uint64_t lit = 0, seq = 0;
-    for (uint32_t f = 0; f < nframes; ++f) {
-      FrameRec fr = ws.frames[f];
-      const uint64_t out_n = out_bytes[f];
-      if (fr.status == RPP_OK && (fr.nblocks > ws.max_blocks - base || out_n > ws.lit_cap - lit ||
-                                  out_n / 3 > ws.seq_cap - seq))
-        fr.status = RPP_OUTPUT_TOO_SMALL;
-      if (fr.status == RPP_OK) {
-        fr.block_base = base;
-        fr.lit_base = lit;
-        fr.seq_base = seq;
-        base += fr.nblocks;
-        lit += out_n;
-        seq += out_n / 3;
-      } else {
-        fr.nblocks = 0;
+    // The valid frames first: the promise counts their blocks, and no corrupt frame's blocks may cost one of them
+    // its slots.  Then, from what is left, a corrupt frame's blocks before the failing one, decoded like a valid
+    // frame's; one that does not fit there keeps its status and nothing of it is decoded.
+    for (uint32_t pass = 0; pass < 2; ++pass) {
+      for (uint32_t f = 0; f < nframes; ++f) {
+        FrameRec fr = ws.frames[f];
+        if ((fr.status == RPP_OK) != (pass == 0)) continue;
+        const uint64_t out_n = out_bytes[f];
+        bool run = fr.status == RPP_OK || (fr.status == RPP_CORRUPT_INPUT && fr.nblocks > 0);
+        if (run && (fr.nblocks > ws.max_blocks - base || out_n > ws.lit_cap - lit || out_n / 3 > ws.seq_cap - seq)) {
+          if (fr.status == RPP_OK) fr.status = RPP_OUTPUT_TOO_SMALL;
+          run = false;
+        }
+        if (run) {
+          fr.block_base = base;
+          fr.lit_base = lit;
+          fr.seq_base = seq;
+          base += fr.nblocks;
+          lit += out_n;
+          seq += out_n / 3;
+        } else {
+          fr.nblocks = 0;
+        }
+        ws.frames[f] = fr;
       }
-      ws.frames[f] = fr;
     }
     *ws.used = base;
   }
   __syncthreads();
   for (uint32_t f = threadIdx.x; f < nframes; f += kIndexThreads) {
     FrameRec fr = ws.frames[f];
-    if (fr.status == RPP_OK)
+    if (fr.nblocks)
       walk_frame(d_in + in_offsets[f], in_bytes[f], out_bytes[f], f, fr, ws.blocks + fr.block_base, fr.nblocks);
   }
 }
@@ -296,7 +310,7 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_execute_kernel(
   const uint32_t f = blockIdx.x, lane = lane_id();
   if (f >= nframes) return;
   const FrameRec fr = ws.frames[f];
-  if (fr.status != RPP_OK) {
+  if (fr.nblocks == 0) {  // (a valid frame has a block at least)
     if (lane == 0) d_status[f] = fr.status;
     return;
   }
@@ -365,7 +379,7 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_execute_kernel(
     wave_copy(dst + op, lits + lit_at, rest, lane);
     op += rest;
   }
-  if (lane == 0) d_status[f] = !bad && op == out_n ? RPP_OK : RPP_CORRUPT_INPUT;
+  if (lane == 0) d_status[f] = fr.status == RPP_OK && !bad && op == out_n ? RPP_OK : RPP_CORRUPT_INPUT;
 }
 
 uint64_t align16(uint64_t v) { return (v + 15) & ~UINT64_C(15); }

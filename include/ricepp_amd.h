@@ -1047,7 +1047,13 @@ long rpp_zstd_count_blocks(const uint8_t* data, size_t size);
  * total_out_bytes >= the sum of d_out_bytes (about 5 bytes per output byte).
  * Slots are dealt out frame by frame: a frame with more blocks, or more output,
  * than is left takes none, gets RPP_OUTPUT_TOO_SMALL, and nothing of it is
- * decoded; the frames behind it go on.  max_blocks < nframes returns
+ * decoded; the frames behind it go on.  A frame that rpp_zstd_count_blocks
+ * refuses is promised one block.  Frames that are refused at a block, or for
+ * what follows the last block, get their slots after all other frames, from what
+ * these leave: where the blocks before the failing one fit there, what they
+ * produce is written as rpp_zstd_host_decode writes it, else nothing of the
+ * frame is decoded; RPP_CORRUPT_INPUT either way, and never at the cost of
+ * another frame's slots.  max_blocks < nframes returns
  * RPP_OUTPUT_TOO_SMALL at once; nframes == 0 returns RPP_OK at once.  No
  * initialisation of the workspace is needed.
  */
