@@ -144,6 +144,10 @@ EXPORTED_SYMBOLS = (
     "rpp_zstd_decode_workspace_bytes",
     "rpp_zstd_decode_batch",
     "rpp_zstd_host_decode",
+    "rpp_zstd_bound",
+    "rpp_zstd_encode_workspace_bytes",
+    "rpp_zstd_encode_batch",
+    "rpp_zstd_host_encode",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -488,6 +492,14 @@ def lib() -> C.CDLL:
         L.rpp_zstd_decode_batch.restype = C.c_int
         L.rpp_zstd_host_decode.argtypes = [P, U64, P, U64]
         L.rpp_zstd_host_decode.restype = C.c_int
+        L.rpp_zstd_bound.argtypes = [U64]
+        L.rpp_zstd_bound.restype = U64
+        L.rpp_zstd_encode_workspace_bytes.argtypes = [U64, U32]
+        L.rpp_zstd_encode_workspace_bytes.restype = U64
+        L.rpp_zstd_encode_batch.argtypes = [P, P, P, U32, P, P, P, P, P, U64, P, U64, P]
+        L.rpp_zstd_encode_batch.restype = C.c_int
+        L.rpp_zstd_host_encode.argtypes = [P, U64, P, U64, C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_zstd_host_encode.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

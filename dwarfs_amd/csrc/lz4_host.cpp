@@ -34,21 +34,20 @@
 #include <vector>
 
 #include "lz4_common.h"
+#include "lz4_internal.h"
 #include "ricepp_amd.h"
 
 namespace {
 
 using namespace rpp_lz4;
 
-struct Seq {
-  uint32_t pos, len, off;
-};
-
 inline uint32_t rd32(const uint8_t* p) {
   return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
 }
 
-void find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& seqs) {
+}  // namespace
+
+void rpp_lz4::find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& seqs) {
   if (n < kMatchStartGap + 1) return;
   const uint32_t last_start = n - kMatchStartGap, match_end = n - kLastLiterals;
   std::vector<uint32_t> tab(1u << kHashBits);  // position + 1; 0: empty
@@ -79,6 +78,8 @@ void find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& seqs) {
     }
   }
 }
+
+namespace {
 
 uint8_t* put_length(uint8_t* o, uint32_t v) {  // the extension bytes of a nibble that stands for v >= 15
   for (v -= 15; v >= 255; v -= 255) *o++ = 255;

@@ -20,6 +20,8 @@
 #include <stdint.h>
 
 #include "lz4_common.h"
+#define RPP_LZ4_KERNEL_SIDE
+#include "lz4_internal.h"
 #include "ricepp_amd.h"
 
 namespace {
@@ -156,21 +158,6 @@ __global__ __launch_bounds__(kWave* kDecodeWaves) void rpp_lz4_decode_kernel(
 // ---------------------------------------------------------------------------
 // encode
 // ---------------------------------------------------------------------------
-struct EncodeWs {
-  uint32_t* chunk_base;  // [nblocks + 1] first chunk of block b
-  uint32_t* ok;          // [1] the batch fits the workspace
-  uint32_t* fin_anchor;  // [nblocks] where the block's last literal run starts
-  uint32_t* fin_off;     // [nblocks] ... and its place in the block's output
-  uint32_t* cnt;         // per chunk: sequences
-  uint32_t* first_pos;   //   position of the first match
-  uint32_t* last_end;    //   end of the last match
-  uint32_t* body;        //   bytes of the sequences without the first one's literals
-  uint32_t* carry;       //   end of the last match before the chunk
-  uint32_t* out_off;     //   place of the chunk's first sequence in the block's output
-  uint2* seqs;           // [chunks * kSeqsPerChunk] (pos - chunk start) | offset << 16, length
-  uint32_t max_chunks;
-};
-
 __global__ __launch_bounds__(kWave) void rpp_lz4_prep_kernel(const uint64_t* __restrict__ n_bytes, uint32_t nblocks,
                                                             EncodeWs ws, uint64_t* out_bytes, uint32_t* flags,
                                                             int32_t* status) {
@@ -199,16 +186,6 @@ __global__ __launch_bounds__(kWave) void rpp_lz4_prep_kernel(const uint64_t* __r
   }
   if (!ok)  // the batch is larger than the caller promised: nothing is encoded
     for (uint32_t b = lane; b < nblocks; b += kWave) status[b] = RPP_INVALID_ARGUMENT;
-}
-
-// the block of global chunk g: the last b with chunk_base[b] <= g
-__device__ inline uint32_t block_of_chunk(const uint32_t* chunk_base, uint32_t nblocks, uint32_t g) {
-  uint32_t lo = 0, hi = nblocks;  // chunk_base[lo] <= g < chunk_base[hi]
-  while (hi - lo > 1) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (chunk_base[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 // table entries hold position + 1; the highest value offered for a slot stands
@@ -410,9 +387,41 @@ int launched() { return hipGetLastError() == hipSuccess ? RPP_OK : RPP_HIP_ERROR
 
 uint64_t align16(uint64_t v) { return (v + 15) & ~UINT64_C(15); }
 
-uint64_t max_chunks_of(uint64_t total_bytes, uint32_t nblocks) { return total_bytes / kChunk + nblocks; }
-
 }  // namespace
+
+rpp_lz4::EncodeWs rpp_lz4::carve_workspace(void* d_workspace, uint64_t total_bytes, uint32_t nblocks) {
+  const uint64_t mc = max_chunks_of(total_bytes, nblocks);
+  uint8_t* p = static_cast<uint8_t*>(d_workspace);
+  auto take = [&p](uint64_t bytes) {
+    uint32_t* r = reinterpret_cast<uint32_t*>(p);
+    p += align16(bytes);
+    return r;
+  };
+  EncodeWs ws{};
+  ws.chunk_base = take(4ull * (nblocks + 1));
+  ws.ok = take(16);
+  ws.fin_anchor = take(4ull * nblocks);
+  ws.fin_off = take(4ull * nblocks);
+  ws.cnt = take(4 * mc);
+  ws.first_pos = take(4 * mc);
+  ws.last_end = take(4 * mc);
+  ws.body = take(4 * mc);
+  ws.carry = take(4 * mc);
+  ws.out_off = take(4 * mc);
+  ws.seqs = reinterpret_cast<uint2*>(p);
+  ws.max_chunks = uint32_t(mc);
+  return ws;
+}
+
+void rpp_lz4::launch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                            uint32_t nblocks, const EncodeWs& ws, uint64_t* d_out_bytes, uint32_t* d_flags,
+                            int32_t* d_status, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(rpp_lz4_prep_kernel, dim3(1), dim3(kWave), 0, s, d_in_bytes, nblocks, ws, d_out_bytes, d_flags,
+                     d_status);
+  hipLaunchKernelGGL(rpp_lz4_search_kernel, dim3(ws.max_chunks), dim3(kWave), 0, s, d_in, d_in_offsets, d_in_bytes,
+                     nblocks, ws);
+}
 
 extern "C" int rpp_lz4_decode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
                                     uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets,
@@ -443,30 +452,9 @@ extern "C" int rpp_lz4_encode_batch(const uint8_t* d_in, const uint64_t* d_in_of
   const uint64_t mc = max_chunks_of(total_bytes, nblocks);
   if (mc >= 0x7fffffffu) return RPP_INVALID_ARGUMENT;
   if (workspace_bytes < rpp_lz4_encode_workspace_bytes(total_bytes, nblocks)) return RPP_OUTPUT_TOO_SMALL;
-  uint8_t* p = static_cast<uint8_t*>(d_workspace);
-  auto take = [&p](uint64_t bytes) {
-    uint32_t* r = reinterpret_cast<uint32_t*>(p);
-    p += align16(bytes);
-    return r;
-  };
-  EncodeWs ws{};
-  ws.chunk_base = take(4ull * (nblocks + 1));
-  ws.ok = take(16);
-  ws.fin_anchor = take(4ull * nblocks);
-  ws.fin_off = take(4ull * nblocks);
-  ws.cnt = take(4 * mc);
-  ws.first_pos = take(4 * mc);
-  ws.last_end = take(4 * mc);
-  ws.body = take(4 * mc);
-  ws.carry = take(4 * mc);
-  ws.out_off = take(4 * mc);
-  ws.seqs = reinterpret_cast<uint2*>(p);
-  ws.max_chunks = uint32_t(mc);
+  const EncodeWs ws = carve_workspace(d_workspace, total_bytes, nblocks);
+  launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rpp_lz4_prep_kernel, dim3(1), dim3(kWave), 0, s, d_in_bytes, nblocks, ws, d_out_bytes, d_flags,
-                     d_status);
-  hipLaunchKernelGGL(rpp_lz4_search_kernel, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets, d_in_bytes,
-                     nblocks, ws);
   hipLaunchKernelGGL(rpp_lz4_place_kernel, dim3(nblocks), dim3(kWave), 0, s, d_in_bytes, nblocks, ws, d_out,
                      d_out_offsets, d_out_bytes, d_flags, d_status);
   hipLaunchKernelGGL(rpp_lz4_emit_kernel, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets, d_in_bytes,

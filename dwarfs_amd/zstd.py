@@ -1,16 +1,23 @@
-"""DwarFS block decoder for Zstandard over the MI355X kernels (Python mirror).
+"""DwarFS block codec for Zstandard over the MI355X kernels (Python mirror).
 
-Mirrors ``zstd_block_decompressor`` of src/compression/zstd.cpp:443-483.  A compressed DwarFS block is one
+Mirrors ``zstd_block_compressor`` (src/compression/zstd.cpp:320-441), ``zstd_block_decompressor`` (:443-483) and
+the factory registered as ``"zstd"`` with option ``level``.  A compressed DwarFS block is one
 Zstandard frame (RFC 8878), as ``ZSTD_compress2`` writes it (:424-441); the compression type is ZSTD = 2
 (include/dwarfs/compression.h:34-42).  The constructor reads the content size from the frame header, as
 ``ZSTD_getFrameContentSize`` does (:445-460): a frame without it raises ``ZSTD content size unknown``, a header
 that cannot be parsed ``ZSTD content size error``; a failed decode raises
 ``failed to decompress frame (zstd error: <status>)`` (:475-480) with this library's status code.
 
-There is no encoder: ``block_codec.block_compressor("zstd")`` is an unknown compression.  The Content_Checksum
-is skipped, not verified, and dictionaries are refused.  ``device="cpu"`` runs the host restatement of the
-kernels (rpp_zstd_host_decode); the section helpers need the GPU.  Besides the one-block API there is
-``decompress_many``: one batch for many blocks.
+The encoder is this project's own and deterministic (defined at the top of csrc/zstd_encode_host.cpp): one
+frame per block, one Zstandard block per 32 KiB chunk of the LZ4 encoder's match search, predefined sequence
+tables, no repeat offsets, no checksum; ``level`` is recorded and changes nothing.  ``compress`` raises
+:class:`lz4.BadCompressionRatioError` when the frame is no smaller than the input; the writer then stores the
+block as type NONE, which ``compress_many_sections`` does.  ``zstd.block_compressor("zstd[:level=N]")`` makes
+one; ``block_codec.block_compressor("zstd")`` is still an unknown compression.
+
+The Content_Checksum is skipped, not verified, and dictionaries are refused.  ``device="cpu"`` runs the host
+restatements of the kernels (rpp_zstd_host_encode / rpp_zstd_host_decode); the section helpers need the GPU.
+Besides the one-block API there are ``compress_many`` / ``decompress_many``: one batch for many blocks.
 """
 
 from __future__ import annotations
@@ -24,7 +31,8 @@ import torch
 from . import _native as N
 from . import section as S
 from .codec import _raise_status, _stream_ptr
-from .lz4 import _layout, _ptr, _upload
+from .lz4 import (COMPRESSION_TYPE_NONE, MAX_BLOCK, BadCompressionRatioError, EncodedBatch, _layout, _ptr,
+                  _upload)
 
 COMPRESSION_TYPE_ZSTD = 2  # include/dwarfs/compression.h:34-42
 FLAG_SINGLE_SEGMENT, FLAG_CHECKSUM, FLAG_CONTENT_SIZE = 1, 2, 4
@@ -158,3 +166,151 @@ def decompress_many(decs: Sequence[ZstdBlockDecompressor], device="cuda") -> Lis
     for st in status.cpu().numpy():
         raise_decode_status(int(st))
     return [host[o:o + n].tobytes() for o, n in zip(out_offs, sizes)]
+
+
+def bound(n: int) -> int:
+    return int(N.lib().rpp_zstd_bound(int(n)))
+
+
+def host_encode(data: bytes):
+    """``rpp_zstd_host_encode``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
+    src = np.frombuffer(bytes(data) + b"\0", np.uint8)
+    cap = bound(len(src) - 1)
+    out = np.zeros(cap, np.uint8)
+    n, flag = C.c_uint64(), C.c_uint32()
+    _raise_status(N.lib().rpp_zstd_host_encode(src.ctypes.data_as(C.c_void_p), len(src) - 1,
+                                               out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(flag)))
+    return out[:n.value].tobytes(), bool(flag.value)
+
+
+def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
+                 stream: Optional[torch.cuda.Stream] = None) -> EncodedBatch:
+    """One ``rpp_zstd_encode_batch`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
+    tensor; host lists of offsets and sizes): one frame per block; ``flags`` is 1 where size >= input size.
+    Asynchronous on the stream."""
+    dev = d_in.device
+    n = len(in_sizes)
+    for s in in_sizes:
+        if s > MAX_BLOCK:
+            raise ValueError(f"a block holds at most {MAX_BLOCK} bytes, not {s}")
+    out_offs, cap = _layout([bound(s) for s in in_sizes])
+    total = int(sum(int(s) for s in in_sizes))
+    d_ioff, d_isz, d_ooff = S._i64(in_offsets, dev), S._i64(list(in_sizes), dev), S._i64(out_offs, dev)
+    out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+    sizes = torch.zeros(n, dtype=torch.int64, device=dev)
+    flags = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.int32, device=dev)
+    ws_bytes = int(N.lib().rpp_zstd_encode_workspace_bytes(total, n))
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    _raise_status(N.lib().rpp_zstd_encode_batch(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, _ptr(out), _ptr(d_ooff),
+                                                _ptr(sizes), _ptr(flags), _ptr(status), total, _ptr(ws), ws_bytes,
+                                                _stream_ptr(stream)))
+    return EncodedBatch(out, d_ooff, sizes, flags, status, d_in, d_ioff, d_isz)
+
+
+class ZstdBlockCompressor:
+    """``zstd_block_compressor`` (src/compression/zstd.cpp:320-441).  ``level`` (at most 22, ZSTD_maxCLevel) is
+    recorded and does not change the search."""
+
+    def __init__(self, level: int = 22, device="cuda"):
+        if int(level) > 22:
+            raise RuntimeError(f"invalid option(s) for zstd: level={level}")
+        self.level = int(level)
+        self.device = torch.device(device)
+
+    def clone(self) -> "ZstdBlockCompressor":
+        return ZstdBlockCompressor(self.level, self.device)
+
+    def type(self) -> int:
+        return COMPRESSION_TYPE_ZSTD
+
+    def describe(self) -> str:
+        return f"zstd [level={self.level}]"  # zstd.cpp:329-331
+
+    def metadata_requirements(self) -> str:
+        return ""
+
+    def get_compression_constraints(self, metadata: Optional[str] = None) -> dict:
+        return {}
+
+    def estimate_memory_usage(self, data_size: int) -> int:
+        return data_size
+
+    def _encode(self, blocks: Sequence[bytes]) -> EncodedBatch:
+        d_in, offs = _upload(blocks, self.device)
+        return encode_batch(d_in, offs, [len(b) for b in blocks])
+
+    def compress(self, data: bytes, metadata: Optional[str] = None) -> bytes:
+        out = self.compress_many([data], metadata, keep_bad=True)[0]
+        if out is None:
+            raise BadCompressionRatioError()
+        return out
+
+    def compress_many(self, blocks: Sequence[bytes], metadata: Optional[str] = None,
+                      keep_bad: bool = False) -> List[Optional[bytes]]:
+        """Compresses many blocks in one batch.  A block that trips the ratio rule raises
+        :class:`lz4.BadCompressionRatioError`, or with ``keep_bad`` comes back as None."""
+        if not blocks:
+            return []
+        if self.device.type == "cpu":  # the host restatement: the kernels' bytes without a GPU
+            frames, flags = zip(*(host_encode(b) for b in blocks))
+        else:
+            res = self._encode(blocks)
+            torch.cuda.current_stream().synchronize()
+            res.check()
+            sizes, flags, offs = res.sizes.cpu().numpy(), res.flags.cpu().numpy(), res.offsets.cpu().numpy()
+            data = res.data.cpu().numpy()
+            frames = [data[o:o + n].tobytes() for o, n in zip(offs, sizes)]
+        out: List[Optional[bytes]] = []
+        for frame, flag in zip(frames, flags):
+            if flag and not keep_bad:
+                raise BadCompressionRatioError()
+            out.append(None if flag else frame)
+        return out
+
+    def compress_many_sections(self, blocks: Sequence[bytes], metadata: Optional[str] = None,
+                               first_number: int = 0) -> bytes:
+        """Compresses many blocks and returns them as image-ready BLOCK sections, numbered from
+        ``first_number``.  A block that trips the ratio rule becomes a NONE section (type 0, the raw bytes as
+        payload), as the writer does (src/writer/filesystem_writer.cpp:282-284).  Encode, checksums and
+        assembly run on the device; the sizes and ratio flags come to the host once in between."""
+        if not blocks:
+            return b""
+        res = self._encode(blocks)
+        torch.cuda.current_stream().synchronize()
+        res.check()
+        sizes, flags = res.sizes.cpu().numpy(), res.flags.cpu().numpy().astype(bool)
+        enc_offs, in_offs = res.offsets.cpu().numpy(), res.in_offsets.cpu().numpy()
+        payload = torch.cat([res.data, res.source])  # a NONE section's payload is the input itself
+        offs = np.where(flags, res.data.numel() + in_offs, enc_offs)
+        lens = np.where(flags, [len(b) for b in blocks], sizes)
+        headers, i = [], 0
+        while i < len(blocks):  # one header launch per run of sections of the same compression type
+            j = i
+            while j < len(blocks) and flags[j] == flags[i]:
+                j += 1
+            headers.append(S.section_headers_batch(payload, offs[i:j], lens[i:j], first_number + i, S.SECTION_TYPE_BLOCK,
+                                                   COMPRESSION_TYPE_NONE if flags[i] else self.type()))
+            i = j
+        capacity = int(lens.sum()) + len(blocks) * S.HEADER_BYTES
+        asm = S.sections_assemble_batch(torch.cat(headers), payload, offs, lens, capacity)  # (no DwarFS framing)
+        return asm.bytes()
+
+
+def block_compressor(spec: str, device="cuda") -> ZstdBlockCompressor:
+    """The factory for ``zstd[:level=N]``; any other option raises ``invalid option(s) for zstd: ...``."""
+    name, *opts = spec.split(":")
+    if name != "zstd":
+        raise RuntimeError(f"unknown compression: {name}")
+    level, bad = 22, []
+    for opt in opts:
+        key, _, value = opt.partition("=")
+        try:
+            if key != "level" or int(value) > 22:
+                raise ValueError
+            level = int(value)
+        except ValueError:
+            bad.append(opt)
+    if bad:
+        raise RuntimeError("invalid option(s) for zstd: " + ", ".join(bad))
+    return ZstdBlockCompressor(level, device)

@@ -992,8 +992,8 @@ int rpp_lz4_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t ca
                         uint32_t* bad_ratio);
 
 /*
- * zstd: the Zstandard block decoder (src/compression/zstd.cpp:443-483),
- * compression type ZSTD = 2 (include/dwarfs/compression.h:34-42).  No encoder.
+ * zstd: the Zstandard block codec (src/compression/zstd.cpp:424-483),
+ * compression type ZSTD = 2 (include/dwarfs/compression.h:34-42).
  *
  *   payload   ONE Zstandard frame (RFC 8878), as ZSTD_compress2 writes it
  *             (zstd.cpp:424-441): single-segment or with a Window_Descriptor,
@@ -1021,7 +1021,20 @@ int rpp_lz4_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t ca
  *             Frames and contents hold less than 4 GiB each: a larger one gets
  *             RPP_INVALID_ARGUMENT in its status.
  *
- * rpp_zstd_decode_batch takes device pointers and is asynchronous on `stream`.
+ *   encode    a deterministic encoder of its own: ONE frame per block, one
+ *             Zstandard block per 32 KiB chunk of the LZ4 encoder's match
+ *             search (same sequences), Huffman literals and FSE sequences with
+ *             the three Predefined tables.  Four launches behind the search's
+ *             two: entropy (one wave per chunk), place (one wave per frame),
+ *             emit (one wave per chunk).  The complete definition is at the top
+ *             of dwarfs_amd/csrc/zstd_encode_host.cpp.  Not libzstd's bytes; any
+ *             Zstandard decoder reads them.  Limits: predefined tables only, no
+ *             repeat offsets, 32 KiB blocks, a 64 KiB match window, no
+ *             compression level, no Content_Checksum.  Blocks hold at most
+ *             RPP_LZ4_MAX_BLOCK bytes: a longer one gets RPP_INVALID_ARGUMENT
+ *             in its status.
+ *
+ * The *_batch calls take device pointers and are asynchronous on `stream`.
  */
 #define RPP_ZSTD_FLAG_SINGLE_SEGMENT 1u
 #define RPP_ZSTD_FLAG_CHECKSUM 2u
@@ -1065,6 +1078,31 @@ int rpp_zstd_decode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, con
 
 /* The kernels' contract as sequential host code (host memory): the CPU path and the yardstick. */
 int rpp_zstd_host_decode(const uint8_t* in, uint64_t in_bytes, uint8_t* out, uint64_t out_bytes);
+
+/* Worst-case bytes of an n-byte block's frame: every chunk stored Raw, plus the frame header. */
+uint64_t rpp_zstd_bound(uint64_t n);
+
+/*
+ * Encodes nblocks blocks: block b is d_in[d_in_offsets[b] .. + d_in_bytes[b]) and
+ * its frame goes to d_out + d_out_offsets[b], a region of rpp_zstd_bound(n) bytes;
+ * d_out_bytes[b] is its size, d_flags[b] is 1 when size >= n (the writer's
+ * bad_compression_ratio_error, zstd.cpp:435: store the block as NONE) and else 0.
+ * The caller owns the 16-aligned workspace of rpp_zstd_encode_workspace_bytes(
+ * total_bytes, nblocks) bytes, total_bytes >= the sum of d_in_bytes; if the device
+ * finds the sum larger, every status is RPP_INVALID_ARGUMENT and nothing is
+ * encoded.  nblocks == 0 returns RPP_OK at once.  No initialisation of the
+ * workspace is needed.
+ */
+uint64_t rpp_zstd_encode_workspace_bytes(uint64_t total_bytes, uint32_t nblocks);
+int rpp_zstd_encode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                          uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets, uint64_t* d_out_bytes,
+                          uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                          uint64_t workspace_bytes, void* stream);
+
+/* The encode kernels' contract as sequential host code (host memory): exactly their bytes.  capacity must be
+ * at least rpp_zstd_bound(n), else RPP_OUTPUT_TOO_SMALL. */
+int rpp_zstd_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
+                         uint32_t* bad_ratio);
 
 #ifdef __cplusplus
 }
