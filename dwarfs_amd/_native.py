@@ -148,11 +148,16 @@ EXPORTED_SYMBOLS = (
     "rpp_zstd_encode_workspace_bytes",
     "rpp_zstd_encode_batch",
     "rpp_zstd_host_encode",
+    "rpp_zstd_encode_batch_opt",
+    "rpp_zstd_host_encode_opt",
 )
 
 RPP_HASH_XXH3_64 = 0
 RPP_HASH_XXH3_128 = 1
 RPP_HASH_SHA512_256 = 2
+
+RPP_ZSTD_ENC_TABLES = 1  # the options word of rpp_zstd_encode_batch_opt / rpp_zstd_host_encode_opt
+RPP_ZSTD_ENC_REPEAT = 2
 
 RPP_SIMILARITY_NILSIMSA = 0
 RPP_SIMILARITY_HISTOGRAM = 1
@@ -500,6 +505,10 @@ def lib() -> C.CDLL:
         L.rpp_zstd_encode_batch.restype = C.c_int
         L.rpp_zstd_host_encode.argtypes = [P, U64, P, U64, C.POINTER(U64), C.POINTER(U32)]
         L.rpp_zstd_host_encode.restype = C.c_int
+        L.rpp_zstd_encode_batch_opt.argtypes = [P, P, P, U32, U32, P, P, P, P, P, U64, P, U64, P]
+        L.rpp_zstd_encode_batch_opt.restype = C.c_int
+        L.rpp_zstd_host_encode_opt.argtypes = [P, U64, U32, P, U64, C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_zstd_host_encode_opt.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

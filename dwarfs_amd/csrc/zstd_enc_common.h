@@ -1,8 +1,9 @@
 // zstd_enc_common.h -- every rule that the Zstandard encode kernels
 // (zstd_encode.hip) and their host restatement (zstd_encode_host.cpp) share, so
 // that the two write the same bytes: the frame, block and section headers, the
-// Huffman code lengths and the tree description, the FSE encoding tables, and
-// the codes of a sequence.  The format they add up to is defined at the top of
+// Huffman code lengths and the tree description, the FSE encoding tables, the
+// codes of a sequence, and, for the options word, the repeat-offset rule and
+// the choice of a block's table modes.  The format they add up to is defined at the top of
 // zstd_encode_host.cpp.  Plain C++, no HIP; sequential functions that a single
 // lane may run on the device.
 #ifndef RPP_ZSTD_ENC_COMMON_H
@@ -18,6 +19,11 @@ constexpr uint32_t kOneStreamMax = 1023;         // literals of a block that go 
 constexpr uint32_t kDirectMax = 128;             // weights the direct tree description can list
 constexpr uint32_t kTreeSlots = 320;             // bytes a tree description is built in (kept: below 129)
 constexpr uint32_t kSeqInitBits = 6 + 5 + 6;     // the three predefined tables' first states
+constexpr uint32_t kEncTables = 1, kEncRepeat = 2;  // the options word (RPP_ZSTD_ENC_TABLES, RPP_ZSTD_ENC_REPEAT)
+constexpr uint32_t kEncOptionsMask = kEncTables | kEncRepeat;
+constexpr uint32_t kOwnLogMax = 6;               // accuracy log of a block's own table, at most: a move of a state
+                                                 // is val | nb << 6 in 9 bits, and the tables stay 64 cells
+constexpr uint32_t kDescSlots = 72;              // bytes a table description is built in (at most 54 are kept)
 static_assert(kEncChunk <= kBlockMax, "a chunk is one block");
 
 RPP_ZSTD_HD uint32_t chunks_of(uint64_t n) { return uint32_t((n + kEncChunk - 1) / kEncChunk); }
@@ -188,12 +194,13 @@ struct TreeScratch {
   uint16_t next[16], cum[16], cells[1u << kHufWeightLog];
 };
 
-// The normalised distribution of the weights' counts (count[0 .. nsym), `total` weights) for a table of
-// 2^kHufWeightLog cells: every value seen gets max(1, count * size / total) rounded down; what is missing goes
-// to the value seen most often (the smallest such value); what is too much is taken one by one from the value
-// with the largest share (the smallest such value).  False for fewer than two values seen.
-RPP_ZSTD_HD bool weight_distribution(const uint32_t* count, uint32_t nsym, uint32_t total, int16_t* freq) {
-  const int32_t size = 1 << kHufWeightLog;
+// The normalised distribution of counts (count[0 .. nsym), `total` together) for a table of 2^log cells: every
+// value seen gets max(1, count * size / total) rounded down; what is missing goes to the value seen most often
+// (the smallest such value); what is too much is taken one by one from the value with the largest share (the
+// smallest such value; it holds at least 2 while no more values are seen than the table has cells).  False for
+// fewer than two values seen.
+RPP_ZSTD_HD bool fse_normalise(const uint32_t* count, uint32_t nsym, uint32_t total, uint32_t log, int16_t* freq) {
+  const int32_t size = 1 << log;
   int32_t sum = 0;
   uint32_t seen = 0, most = 0;
   for (uint32_t v = 0; v < nsym; ++v) {
@@ -214,6 +221,11 @@ RPP_ZSTD_HD bool weight_distribution(const uint32_t* count, uint32_t nsym, uint3
     --freq[top];
   }
   return true;
+}
+
+// the weights' counts (count[0 .. nsym), `total` weights) for a table of 2^kHufWeightLog cells
+RPP_ZSTD_HD bool weight_distribution(const uint32_t* count, uint32_t nsym, uint32_t total, int16_t* freq) {
+  return fse_normalise(count, nsym, total, kHufWeightLog, freq);
 }
 
 // The description of a distribution without "less than 1" probabilities (RFC 8878 4.1.1) at p (zeroed); its bytes.
@@ -396,6 +408,106 @@ RPP_ZSTD_HD uint32_t seq_step(const SeqTables& tabs, uint32_t k, uint32_t code, 
                               uint32_t& nb) {
   const uint32_t e = tabs.info[k][code];
   return fse_enc_step(e & 255, e >> 8, tabs.cells[k], seq_table_log(k), next, val, nb);
+}
+
+// ---------------------------------------------------------------------------
+// sequences with options: repeat offsets (kEncRepeat)
+// ---------------------------------------------------------------------------
+// The offset value of sequence i of its chunk (counted from 0) with the offset `off` and ll literals; off1 and
+// off2 are the offsets of the sequences i - 1 and i - 2 of the same chunk (not read where i is too small).
+//   R1  i >= 1, ll > 0, off == off1                 -> 1 (Repeated_Offset1)
+//   R2  i >= 2, off == off2, off != off1            -> 2 with literals, 1 without (both: Repeated_Offset2)
+//   else                                            -> off + 3
+// A chunk's first sequence is always written in full, the value 3 and Repeated_Offset3 never.  Two invariants of
+// the decoder's history (RFC 8878 3.1.1.5) make the rules safe without looking further back than two sequences,
+// and so without any state that crosses a chunk:
+//   I1  after any sequence, Repeated_Offset1 is that sequence's offset: a full offset and R2 put it there, R1
+//       leaves the history as it is, and the history's first entry was off1 == off;
+//   I2  after a sequence j >= 1 of a chunk with off_j != off_{j-1}, Repeated_Offset2 is off_{j-1}: by I1 it was
+//       Repeated_Offset1 before j, and both a full offset and R2 move Repeated_Offset1 to the second place.
+// R1 reads I1 after sequence i - 1.  R2 reads I2 after j = i - 1 >= 1: off_{i-1} != off_{i-2} follows from
+// off_i == off_{i-2} and off_i != off_{i-1}.
+RPP_ZSTD_HD uint32_t offset_value(uint32_t off, uint32_t off1, uint32_t off2, uint32_t ll, uint32_t i) {
+  if (i >= 1 && off == off1) return ll ? 1 : off + 3;
+  if (i >= 2 && off == off2) return ll ? 2 : 1;
+  return off + 3;
+}
+
+// ---------------------------------------------------------------------------
+// sequences with options: the table modes of a block (kEncTables)
+// ---------------------------------------------------------------------------
+// The accuracy log of a block's own table: 5, or kOwnLogMax = 6 for more than 64 sequences or more than 16 codes
+// seen.  (The format allows 9, 8 and 9; the cap keeps a state's move in the 9 bits of its record.)
+RPP_ZSTD_HD uint32_t own_table_log(uint32_t count, uint32_t seen) { return count > 64 || seen > 16 ? kOwnLogMax : 5; }
+
+// What a code of probability f in a table of 2^log cells costs in state bits, in 1/256 bit:
+// log - log2(f), the logarithm's fraction taken as linear between two powers of two.
+RPP_ZSTD_HD uint32_t fse_symbol_cost(uint32_t f, uint32_t log) {
+  const uint32_t hb = highbit(f);
+  return ((log - hb) << 8) - (((f << 8) >> hb) - 256);
+}
+
+struct TablePlan {
+  uint32_t mode, log, desc_bytes;  // desc_bytes: what follows the modes byte for this table (RLE: the code)
+};
+
+RPP_ZSTD_HD TablePlan predefined_plan(uint32_t k) { return TablePlan{kPredefined, seq_table_log(k), 0}; }
+
+// The mode of table k (0 LL, 1 OF, 2 ML) of a block of `count` >= 1 sequences whose codes are counted in
+// hist[kFreqSlots]:
+//   RLE             one code seen: the description is that code, the table has the log 0 and no state bits;
+//   FSE_Compressed  when 8 * the description's bytes + E(own) < E(predefined), where E(d) = 256 * log(d) (the first
+//                   state) + the sum over the codes of count * fse_symbol_cost under d, the own distribution being
+//                   fse_normalise's at own_table_log; `tabs` then gets table k's encoding side;
+//   Predefined      otherwise; `tabs` is left alone (the caller put the predefined table there).
+// Never Repeat_Mode.  desc[kDescSlots] gets the description; t[64], freq, next, cum [kFreqSlots] are scratch.
+RPP_ZSTD_HD TablePlan plan_table(uint32_t k, const uint32_t* hist, uint32_t count, SeqTables& tabs, uint8_t* desc,
+                                 FseEntry* t, int16_t* freq, uint16_t* next, uint16_t* cum) {
+  uint32_t nsym = 0, seen = 0, pn, plog;
+  for (uint32_t s = 0; s < kFreqSlots; ++s)
+    if (hist[s]) {
+      nsym = s + 1;
+      ++seen;
+    }
+  for (uint32_t i = 0; i < kDescSlots; ++i) desc[i] = 0;
+  if (seen == 1) {
+    desc[0] = uint8_t(nsym - 1);
+    return TablePlan{kModeRle, 0, 1};
+  }
+  predefined(k, freq, pn, plog);
+  uint32_t pre = plog << 8;
+  bool stated = true;  // (the search's codes all have a predefined probability: offset codes stay below 16)
+  for (uint32_t s = 0; s < nsym; ++s)
+    if (hist[s]) {
+      if (s >= pn || freq[s] == 0) stated = false;
+      else pre += hist[s] * fse_symbol_cost(freq[s] == -1 ? 1u : uint32_t(freq[s]), plog);
+    }
+  const uint32_t log = own_table_log(count, seen);
+  fse_normalise(hist, nsym, count, log, freq);
+  const uint32_t bytes = fse_write_description(freq, nsym, log, desc);
+  uint32_t own = (8 * bytes + log) << 8;
+  for (uint32_t s = 0; s < nsym; ++s)
+    if (hist[s]) own += hist[s] * fse_symbol_cost(uint32_t(freq[s]), log);
+  if (stated && own >= pre) return predefined_plan(k);
+  fse_build(freq, nsym, log, t, next);
+  fse_enc_build(t, freq, nsym, log, cum, tabs.cells[k]);
+  for (uint32_t s = 0; s < nsym; ++s) tabs.info[k][s] = uint16_t(uint32_t(freq[s]) | cum[s] << 8);
+  return TablePlan{kFse, log, bytes};
+}
+
+// seq_last_state and seq_step for a table of the accuracy log `log` (0: RLE, one state and no bits)
+RPP_ZSTD_HD uint32_t seq_last_state_own(const SeqTables& tabs, uint32_t k, uint32_t log, uint32_t code) {
+  return log ? tabs.cells[k][tabs.info[k][code] >> 8] : 0;
+}
+
+RPP_ZSTD_HD uint32_t seq_step_own(const SeqTables& tabs, uint32_t k, uint32_t log, uint32_t code, uint32_t next,
+                                  uint32_t& val, uint32_t& nb) {
+  if (!log) {
+    val = nb = 0;
+    return 0;
+  }
+  const uint32_t e = tabs.info[k][code];
+  return fse_enc_step(e & 255, e >> 8, tabs.cells[k], log, next, val, nb);
 }
 
 }  // namespace rpp_zstd

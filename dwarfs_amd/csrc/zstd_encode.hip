@@ -26,6 +26,18 @@
 // memory; everything else about a sequence is recomputed in parallel.
 // No global atomics.  Variable shifts are 32-bit ("64-bit
 // shifts and the last VGPR").
+//
+// The entropy kernel is a template on "options != 0" (rpp_zstd_encode_batch_opt).
+// The `false` instantiation is the code path above and writes its bytes.  The
+// `true` one adds, where the options word asks for it: the offsets of the two
+// sequences before (a lane shuffle, and across a tile of 64 the carry of the
+// tile's last two offsets) for the repeat-offset rule; LDS histograms of the
+// three code alphabets; the table modes, chosen and built by lanes 0 to 2, one
+// table each, with the shared sequential function plan_table; the descriptions
+// behind the modes byte; and chains and first states in each table's own log.
+// A state's move stays val | nb << 6 in 9 bits of the `tr` record because the
+// own tables' accuracy log is capped at 6 (kOwnLogMax: val and nb are at most
+// 6 bits and 6), so the workspace is the same for every options word.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,8 +56,9 @@ using rpp_lz4::kSeqsPerChunk;
 constexpr uint32_t kWave = 64;
 constexpr uint32_t kWinWords = 1024;  // the LDS window
 constexpr uint32_t kTileBits = 4096;  // what one turn adds, at most: 256 codes of 11 bits, 64 sequences of 62
-constexpr uint32_t kLitsPerLane = 4;
-static_assert(kWave * kLitsPerLane * kHufLog <= kTileBits && kWave * 62 <= kTileBits, "a turn fits the window");
+constexpr uint32_t kLitsPerLane = 4;  // (with own tables 63: three moves of kOwnLogMax bits, 15 extra bits thrice)
+static_assert(kWave * kLitsPerLane * kHufLog <= kTileBits && kWave * (3 * kOwnLogMax + 45) <= kTileBits,
+              "a turn fits the window");
 
 struct ZstdWs {
   uint8_t* lits;   // per chunk: [kEncChunk] its literals
@@ -185,13 +198,23 @@ __device__ inline SeqView seq_view(const uint2* seqs, uint32_t i, uint32_t cs) {
   return SeqView{cs + (s.x & 0xffffu) - prev, s.y, (s.x >> 16) + 3};
 }
 
+// ... with the offset value of the repeat-offset rule
+__device__ inline SeqView seq_view_repeat(const uint2* seqs, uint32_t i, uint32_t cs) {
+  SeqView v = seq_view(seqs, i, cs);
+  const uint32_t off1 = i >= 1 ? seqs[i - 1].x >> 16 : 0, off2 = i >= 2 ? seqs[i - 2].x >> 16 : 0;
+  v.ov = offset_value(v.ov - 3, off1, off2, v.ll, i);
+  return v;
+}
+
 // ---------------------------------------------------------------------------
 // entropy: one wave per chunk
 // ---------------------------------------------------------------------------
+template <bool kOpt>  // kOpt: options != 0
 __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8_t* __restrict__ d_in,
                                                                 const uint64_t* __restrict__ in_offsets,
                                                                 const uint64_t* __restrict__ n_bytes,
-                                                                uint32_t nblocks, EncodeWs ws, ZstdWs zws) {
+                                                                uint32_t nblocks, EncodeWs ws, ZstdWs zws,
+                                                                uint32_t options) {
   __shared__ uint32_t win_words[kWinWords], hist[256], ctab[256], shared[2];
   __shared__ uint8_t lens[256], desc[kTreeSlots];
   __shared__ TreeScratch sc;
@@ -199,6 +222,8 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
   __shared__ FseEntry build_t[3][64];
   __shared__ int16_t build_freq[3][kFreqSlots];
   __shared__ uint16_t build_next[3][kFreqSlots], build_cum[3][kFreqSlots];
+  __shared__ uint32_t code_hist[3][kFreqSlots], table_plan[3][3];  // (kOpt only) per table: mode, log, description bytes
+  __shared__ uint8_t table_desc[3][kDescSlots];                    // (kOpt only)
   const uint32_t g = blockIdx.x, lane = lane_id();
   if (!*ws.ok || g >= ws.chunk_base[nblocks]) return;
   const uint32_t b = block_of_chunk(ws.chunk_base, nblocks, g);
@@ -212,11 +237,14 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
   uint32_t* const tr = zws.tr + uint64_t(g) * kSeqsPerChunk;
 
   for (uint32_t s = lane; s < 256; s += kWave) hist[s] = 0;
+  if constexpr (kOpt)
+    for (uint32_t k = 0; k < 3; ++k) code_hist[k][lane] = 0;
   if (lane < 3) seq_table_build(lane, tabs, build_t[lane], build_freq[lane], build_next[lane], build_cum[lane]);
   __syncthreads();
 
   // the literals: a run of up to 64 bytes by its lane, a longer one by the wave; the codes of every sequence
   uint32_t m = 0, prev_end = cs, extra_bits = 0;
+  [[maybe_unused]] uint32_t off_carry1 = 0, off_carry2 = 0;  // the offsets of the last two sequences of the tile before
   for (uint32_t t = 0; t < cnt; t += kWave) {
     const uint32_t i = t + lane, here = min(cnt - t, kWave);
     const bool has = i < cnt;
@@ -227,10 +255,26 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
     if (lane == 0) prev = prev_end;
     const uint32_t lit = has ? pos - prev : 0;
     const uint32_t incl = wave_incl_sum(lit, lane), mine = m + incl - lit;
+    uint32_t ov = (s.x >> 16) + 3;
+    if constexpr (kOpt) {
+      const uint32_t off = s.x >> 16;
+      uint32_t off1 = __shfl_up(off, 1), off2 = __shfl_up(off, 2);
+      if (lane == 0) off1 = off_carry1;
+      if (lane < 2) off2 = lane == 0 ? off_carry2 : off_carry1;
+      if (has && (options & kEncRepeat)) ov = offset_value(off, off1, off2, lit, i);
+      off_carry1 = uint32_t(__shfl(off, int(kWave - 1)));  // (read only behind a full tile)
+      off_carry2 = uint32_t(__shfl(off, int(kWave - 2)));
+    }
     if (has) {
-      const SeqCodes c = sequence_codes(lit, len, (s.x >> 16) + 3);
+      const SeqCodes c = sequence_codes(lit, len, ov);
       extra_bits += c.llb + c.mlb + c.ofb;
       tr[i] = c.llc | c.ofc << 6 | c.mlc << 12;
+      if constexpr (kOpt)
+        if (options & kEncTables) {
+          atomicAdd(&code_hist[0][c.llc], 1u);
+          atomicAdd(&code_hist[1][c.ofc], 1u);
+          atomicAdd(&code_hist[2][c.mlc], 1u);
+        }
       if (lit <= kWave)
         for (uint32_t j = 0; j < lit; ++j) {
           const uint32_t v = in[prev + j];
@@ -283,8 +327,28 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
 
   // the three state chains, side by side in lanes 0 to 2 (the other lanes repeat them), from the last sequence
   uint32_t seq_bytes = 1, first_state[3] = {0, 0, 0};
+  [[maybe_unused]] uint32_t tmode[3] = {0, 0, 0}, tlog[3] = {6, 5, 6}, tdesc[3] = {0, 0, 0};
+  if constexpr (kOpt)
+    if (cnt) {  // the table modes: lanes 0 to 2 choose and build one table each (tabs holds the predefined ones)
+      if (lane < 3) {
+        TablePlan p = predefined_plan(lane);
+        if (options & kEncTables)
+          p = plan_table(lane, code_hist[lane], cnt, tabs, table_desc[lane], build_t[lane], build_freq[lane],
+                         build_next[lane], build_cum[lane]);
+        table_plan[lane][0] = p.mode;
+        table_plan[lane][1] = p.log;
+        table_plan[lane][2] = p.desc_bytes;
+      }
+      __syncthreads();
+      for (uint32_t q = 0; q < 3; ++q) {
+        tmode[q] = table_plan[q][0];
+        tlog[q] = table_plan[q][1];
+        tdesc[q] = table_plan[q][2];
+      }
+    }
   if (cnt) {
     const uint32_t k = lane % 3;
+    [[maybe_unused]] const uint32_t my_log = k == 0 ? tlog[0] : k == 1 ? tlog[1] : tlog[2];
     uint32_t st = 0, state_bits = 0;
     for (uint32_t tile = (cnt - 1) / kWave * kWave;; tile -= kWave) {
       const uint32_t i = tile + lane, here = min(cnt - tile, kWave);
@@ -294,10 +358,12 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
         const uint32_t code = uint32_t(__shfl(codes, int(j))) >> (6 * k) & 63;
         uint32_t mine = 0;
         if (tile + j == cnt - 1) {
-          st = seq_last_state(tabs, k, code);
+          if constexpr (kOpt) st = seq_last_state_own(tabs, k, my_log, code);
+          else st = seq_last_state(tabs, k, code);
         } else {
           uint32_t val, nb;
-          st = seq_step(tabs, k, code, st, val, nb);
+          if constexpr (kOpt) st = seq_step_own(tabs, k, my_log, code, st, val, nb);
+          else st = seq_step(tabs, k, code, st, val, nb);
           mine = val | nb << 6;
           state_bits += nb;
         }
@@ -307,12 +373,13 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
       if (i < cnt) tr[i] = out;
       if (tile == 0) break;
     }
-    uint32_t total_bits = kSeqInitBits + extra_bits;
+    uint32_t total_bits = (kOpt ? tlog[0] + tlog[1] + tlog[2] : kSeqInitBits) + extra_bits;
     for (uint32_t q = 0; q < 3; ++q) {
       first_state[q] = uint32_t(__shfl(st, int(q)));
       total_bits += uint32_t(__shfl(state_bits, int(q)));
     }
     seq_bytes = sequence_count_bytes(cnt, nullptr) + 1 + (total_bits >> 3) + 1;
+    if constexpr (kOpt) seq_bytes += tdesc[0] + tdesc[1] + tdesc[2];
     wave_publish();
   }
 
@@ -358,11 +425,16 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
     if (lane == 0) q[0] = 0;
     return;
   }
-  const uint32_t head = sequence_count_bytes(cnt, nullptr) + 1;
+  uint32_t head = sequence_count_bytes(cnt, nullptr) + 1;
   if (lane == 0) {
     sequence_count_bytes(cnt, q);
-    q[head - 1] = 0;  // three Predefined tables
+    q[head - 1] = kOpt ? uint8_t(tmode[0] << 6 | tmode[1] << 4 | tmode[2] << 2) : 0;  // 0: three Predefined tables
   }
+  if constexpr (kOpt)
+    for (uint32_t k = 0; k < 3; ++k) {  // the descriptions in LL, OF, ML order
+      if (lane < tdesc[k]) q[head + lane] = table_desc[k][lane];
+      head += tdesc[k];
+    }
   Win win;
   win_open(win, win_words, q + head, lane);
   uint32_t pos = 0;
@@ -373,7 +445,9 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
     SeqCodes c{};
     uint32_t f[3] = {0, 0, 0}, width = 0;
     if (has) {
-      const SeqView v = seq_view(seqs, cnt - 1 - r, cs);
+      SeqView v;
+      if constexpr (kOpt) v = options & kEncRepeat ? seq_view_repeat(seqs, cnt - 1 - r, cs) : seq_view(seqs, cnt - 1 - r, cs);
+      else v = seq_view(seqs, cnt - 1 - r, cs);
       c = sequence_codes(v.ll, v.ml, v.ov);
       const uint32_t moved = tr[cnt - 1 - r];
       for (uint32_t k = 0; k < 3; ++k) f[k] = moved >> (9 * k) & 511;
@@ -397,12 +471,21 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
     pos += uint32_t(__shfl(incl, kWave - 1));
   }
   win_room(win, pos, lane);
-  if (lane == 0) {
-    win_put(win, pos, first_state[2], seq_table_log(2));
-    win_put(win, pos + 6, first_state[1], seq_table_log(1));
-    win_put(win, pos + 11, first_state[0], seq_table_log(0));
+  if constexpr (kOpt) {
+    if (lane == 0) {
+      win_put(win, pos, first_state[2], tlog[2]);
+      win_put(win, pos + tlog[2], first_state[1], tlog[1]);
+      win_put(win, pos + tlog[2] + tlog[1], first_state[0], tlog[0]);
+    }
+    win_close(win, pos + tlog[0] + tlog[1] + tlog[2], lane);
+  } else {
+    if (lane == 0) {
+      win_put(win, pos, first_state[2], seq_table_log(2));
+      win_put(win, pos + 6, first_state[1], seq_table_log(1));
+      win_put(win, pos + 11, first_state[0], seq_table_log(0));
+    }
+    win_close(win, pos + kSeqInitBits, lane);
   }
-  win_close(win, pos + kSeqInitBits, lane);
 }
 
 // ---------------------------------------------------------------------------
@@ -471,6 +554,18 @@ extern "C" int rpp_zstd_encode_batch(const uint8_t* d_in, const uint64_t* d_in_o
                                      uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets,
                                      uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes,
                                      void* d_workspace, uint64_t workspace_bytes, void* stream) {
+  return rpp_zstd_encode_batch_opt(d_in, d_in_offsets, d_in_bytes, nblocks, 0, d_out, d_out_offsets, d_out_bytes, d_flags,
+                                   d_status, total_bytes, d_workspace, workspace_bytes, stream);
+}
+
+static_assert(RPP_ZSTD_ENC_TABLES == kEncTables && RPP_ZSTD_ENC_REPEAT == kEncRepeat, "the options word");
+
+extern "C" int rpp_zstd_encode_batch_opt(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                                         uint32_t nblocks, uint32_t options, uint8_t* d_out,
+                                         const uint64_t* d_out_offsets, uint64_t* d_out_bytes, uint32_t* d_flags,
+                                         int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                         uint64_t workspace_bytes, void* stream) {
+  if (options & ~kEncOptionsMask) return RPP_INVALID_ARGUMENT;
   if (nblocks == 0) return RPP_OK;
   if (!d_in || !d_in_offsets || !d_in_bytes || !d_out || !d_out_offsets || !d_out_bytes || !d_flags || !d_status ||
       !d_workspace || ((uintptr_t)d_workspace & 15))
@@ -494,8 +589,12 @@ extern "C" int rpp_zstd_encode_batch(const uint8_t* d_in, const uint64_t* d_in_o
   zws.at = reinterpret_cast<uint32_t*>(p);
   rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets, d_in_bytes,
-                     nblocks, ws, zws);
+  if (options)
+    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<true>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
+                       d_in_bytes, nblocks, ws, zws, options);
+  else
+    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<false>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
+                       d_in_bytes, nblocks, ws, zws, options);
   hipLaunchKernelGGL(rpp_zstd_enc_place_kernel, dim3(nblocks), dim3(kWave), 0, s, d_in_bytes, ws, zws, d_out,
                      d_out_offsets, d_out_bytes, d_flags, d_status);
   hipLaunchKernelGGL(rpp_zstd_enc_emit_kernel, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets, nblocks, ws, zws,

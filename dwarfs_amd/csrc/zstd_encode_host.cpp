@@ -5,7 +5,7 @@
 // match search) and zstd_host.cpp (the decoder).  Every rule that both sides
 // need is a function of zstd_enc_common.h; this is the whole definition.
 //
-// Encoder definition (both the kernels and rpp_zstd_host_encode), for a block of
+// Encoder definition (both the kernels and rpp_zstd_host_encode: options 0), for a block of
 // n <= RPP_LZ4_MAX_BLOCK bytes.  The result is ONE RFC 8878 frame; these are not
 // libzstd's bytes, and any Zstandard decoder reads them.
 //   frame      the magic number; a single-segment descriptor; the
@@ -58,6 +58,45 @@
 //              the direct form cannot list the weights (more than 128); else the
 //              direct 4-bit form; else (more than 128 weights, all equal) the
 //              literals are Raw.  No Treeless literals, no Repeat tables.
+// The options word (rpp_zstd_host_encode_opt, rpp_zstd_encode_batch_opt) changes
+// the sequences section only; 0 is everything above, and rpp_zstd_host_encode
+// is that call.  Any bit but the two below is an invalid argument.
+//   repeat     RPP_ZSTD_ENC_REPEAT.  With off_i, ll_i the offset and literal
+//              length of sequence i of a chunk (from 0), offset_value gives
+//                R1  i >= 1, ll_i > 0, off_i == off_{i-1}: offset value 1;
+//                R2  i >= 2, off_i == off_{i-2}, off_i != off_{i-1}: offset
+//                    value 2 when ll_i > 0, value 1 when ll_i == 0 (without
+//                    literals the value 1 means Repeated_Offset2);
+//                else offset + 3.
+//              A chunk's first sequence never uses a repeat code, so no state
+//              crosses a chunk; the value 3 and Repeated_Offset3 are never
+//              written.  The two invariants that make the rules safe are
+//              stated at offset_value.  Codes 0 and 1 (one extra bit, 0).
+//   tables     RPP_ZSTD_ENC_TABLES.  For each of the LL, OF and ML tables of a
+//              block with at least one sequence, plan_table chooses
+//                RLE             every sequence has the same code: the
+//                                description is that code, no state bits;
+//                FSE_Compressed  when 8 * description bytes + E(own) <
+//                                E(predefined), E(d) = 256 * log(d) + the sum
+//                                over the codes of count * fse_symbol_cost (a
+//                                code's cost in 1/256 bit, integer, log2 taken
+//                                as linear between powers of two);
+//                Predefined      otherwise.  Never Repeat_Mode.
+//              The own table's accuracy log (own_table_log) is 5, or 6 for more
+//              than 64 sequences or more than 16 codes seen: capped at
+//              kOwnLogMax = 6 below the format's 9, 8 and 9, so that a state's
+//              move (value and width, 6 bits and 6 at most) keeps the 9 bits it
+//              has in the kernels' workspace record.  Its distribution is
+//              fse_normalise's: every code seen gets max(1, count * size /
+//              total); what is missing goes to the code seen most often, what
+//              is too much is taken one by one from the code with the largest
+//              share; ties by code value; no "less than 1" probabilities.
+//              The section is then: count, modes byte, the descriptions in LL,
+//              OF, ML order (fse_write_description; RLE: the code), bitstream;
+//              the chains as above in the block's tables, the first states
+//              written in their tables' logs (RLE: 0 bits).
+// The block rule (Compressed only when strictly smaller than the chunk) and so
+// rpp_zstd_bound are the same for every options word.
 // The ratio flag is size >= n (zstd_block_compressor::compress's
 // bad_compression_ratio_error, src/compression/zstd.cpp:435).
 #include <algorithm>
@@ -150,8 +189,9 @@ struct Trans {  // what moves the three states from a sequence to the next one
   uint8_t val[3], nb[3];
 };
 
-// The sequences section of a chunk that starts at `cs` at o (zeroed, when `write`); its bytes.
-uint32_t write_sequences(const rpp_lz4::Seq* seqs, uint32_t count, uint32_t cs, const SeqTables& tabs,
+// The sequences section of a chunk that starts at `cs` at o (zeroed, when `write`); its bytes.  `tabs` holds the
+// three predefined tables and is left so; with kEncTables the block's own tables are built in a copy.
+uint32_t write_sequences(const rpp_lz4::Seq* seqs, uint32_t count, uint32_t cs, uint32_t options, const SeqTables& tabs,
                          std::vector<SeqCodes>& codes, std::vector<Trans>& trans, uint8_t* o, bool write) {
   if (count == 0) {
     if (write) o[0] = 0;
@@ -159,30 +199,54 @@ uint32_t write_sequences(const rpp_lz4::Seq* seqs, uint32_t count, uint32_t cs, 
   }
   codes.resize(count);
   trans.resize(count);
-  uint32_t prev = cs, bits = kSeqInitBits;
+  uint32_t prev = cs, bits = 0, hist[3][kFreqSlots] = {};
   for (uint32_t i = 0; i < count; ++i) {
-    codes[i] = sequence_codes(seqs[i].pos - prev, seqs[i].len, seqs[i].off + 3);
+    const uint32_t ll = seqs[i].pos - prev;
+    const uint32_t ov = options & kEncRepeat
+                            ? offset_value(seqs[i].off, i >= 1 ? seqs[i - 1].off : 0, i >= 2 ? seqs[i - 2].off : 0, ll, i)
+                            : seqs[i].off + 3;
+    codes[i] = sequence_codes(ll, seqs[i].len, ov);
     bits += codes[i].llb + codes[i].mlb + codes[i].ofb;
+    ++hist[0][codes[i].llc];
+    ++hist[1][codes[i].ofc];
+    ++hist[2][codes[i].mlc];
     prev = seqs[i].pos + seqs[i].len;
   }
-  uint32_t st[3];
+  TablePlan plan[3] = {predefined_plan(0), predefined_plan(1), predefined_plan(2)};
+  uint8_t desc[3][kDescSlots];
+  SeqTables own;
+  if (options & kEncTables) {
+    own = tabs;
+    FseEntry t[64];
+    int16_t freq[kFreqSlots];
+    uint16_t next[kFreqSlots], cum[kFreqSlots];
+    for (uint32_t k = 0; k < 3; ++k) plan[k] = plan_table(k, hist[k], count, own, desc[k], t, freq, next, cum);
+  }
+  const SeqTables& use = options & kEncTables ? own : tabs;
+  uint32_t st[3], described = 0;
   for (uint32_t k = 0; k < 3; ++k) {
     auto code = [&](uint32_t i) { return k == 0 ? codes[i].llc : k == 1 ? codes[i].ofc : codes[i].mlc; };
-    st[k] = seq_last_state(tabs, k, code(count - 1));
+    st[k] = seq_last_state_own(use, k, plan[k].log, code(count - 1));
     trans[count - 1].nb[k] = 0;
     for (uint32_t i = count - 1; i-- > 0;) {
       uint32_t val, nb;
-      st[k] = seq_step(tabs, k, code(i), st[k], val, nb);
+      st[k] = seq_step_own(use, k, plan[k].log, code(i), st[k], val, nb);
       trans[i].val[k] = uint8_t(val);
       trans[i].nb[k] = uint8_t(nb);
       bits += nb;
     }
+    bits += plan[k].log;  // the first state
+    described += plan[k].desc_bytes;
   }
-  const uint32_t head = sequence_count_bytes(count, nullptr) + 1, total = head + (bits >> 3) + 1;
+  const uint32_t head = sequence_count_bytes(count, nullptr) + 1, total = head + described + (bits >> 3) + 1;
   if (!write) return total;
   sequence_count_bytes(count, o);
-  o[head - 1] = 0;  // three Predefined tables
-  uint8_t* const p = o + head;
+  o[head - 1] = uint8_t(plan[0].mode << 6 | plan[1].mode << 4 | plan[2].mode << 2);  // options 0: 0, all Predefined
+  uint8_t* p = o + head;
+  for (uint32_t k = 0; k < 3; ++k) {  // the descriptions in LL, OF, ML order
+    if (plan[k].desc_bytes) std::memcpy(p, desc[k], plan[k].desc_bytes);
+    p += plan[k].desc_bytes;
+  }
   uint32_t pos = 0;
   auto put = [&](uint32_t v, uint32_t nb) {
     put_bits(p, pos, v, nb);
@@ -198,9 +262,9 @@ uint32_t write_sequences(const rpp_lz4::Seq* seqs, uint32_t count, uint32_t cs, 
     put(c.mlx, c.mlb);
     put(c.ofx, c.ofb);
   }
-  put(st[2], seq_table_log(2));
-  put(st[1], seq_table_log(1));
-  put(st[0], seq_table_log(0));
+  put(st[2], plan[2].log);
+  put(st[1], plan[1].log);
+  put(st[0], plan[0].log);
   put(1, 1);
   return total;
 }
@@ -209,9 +273,16 @@ uint32_t write_sequences(const rpp_lz4::Seq* seqs, uint32_t count, uint32_t cs, 
 
 extern "C" uint64_t rpp_zstd_bound(uint64_t n) { return encode_bound(n); }
 
+static_assert(RPP_ZSTD_ENC_TABLES == kEncTables && RPP_ZSTD_ENC_REPEAT == kEncRepeat, "the options word");
+
 extern "C" int rpp_zstd_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t capacity,
                                     uint64_t* out_bytes, uint32_t* bad_ratio) {
-  if ((n && !in) || !out || !out_bytes) return RPP_INVALID_ARGUMENT;
+  return rpp_zstd_host_encode_opt(in, n, 0, out, capacity, out_bytes, bad_ratio);
+}
+
+extern "C" int rpp_zstd_host_encode_opt(const uint8_t* in, uint64_t n, uint32_t options, uint8_t* out,
+                                        uint64_t capacity, uint64_t* out_bytes, uint32_t* bad_ratio) {
+  if ((n && !in) || !out || !out_bytes || (options & ~kEncOptionsMask)) return RPP_INVALID_ARGUMENT;
   if (n > rpp_lz4::kMaxBlock) return RPP_INVALID_ARGUMENT;
   if (capacity < encode_bound(n)) return RPP_OUTPUT_TOO_SMALL;
   static const Tables tables;
@@ -241,12 +312,12 @@ extern "C" int rpp_zstd_host_encode(const uint8_t* in, uint64_t n, uint8_t* out,
     const uint32_t count = uint32_t(si - s0);
     const rpp_lz4::Seq* const cseqs = seqs.data() + s0;  // (not dereferenced when count == 0)
     const uint32_t lit_bytes = write_literals(lits.data(), m, hist, nullptr, false, nullptr);
-    const uint32_t seq_bytes = write_sequences(cseqs, count, cs, tables.seq, codes, trans, nullptr, false);
+    const uint32_t seq_bytes = write_sequences(cseqs, count, cs, options, tables.seq, codes, trans, nullptr, false);
     const bool last = ce == n;
     if (uint64_t(lit_bytes) + seq_bytes < cn) {
       std::fill(body.begin(), body.begin() + lit_bytes + seq_bytes, uint8_t(0));
       write_literals(lits.data(), m, hist, body.data(), true, nullptr);
-      write_sequences(cseqs, count, cs, tables.seq, codes, trans, body.data() + lit_bytes, true);
+      write_sequences(cseqs, count, cs, options, tables.seq, codes, trans, body.data() + lit_bytes, true);
       block_header(o, last, kCompressed, lit_bytes + seq_bytes);
       std::memcpy(o + 3, body.data(), lit_bytes + seq_bytes);
       o += 3 + lit_bytes + seq_bytes;

@@ -10,7 +10,8 @@ that cannot be parsed ``ZSTD content size error``; a failed decode raises
 
 The encoder is this project's own and deterministic (defined at the top of csrc/zstd_encode_host.cpp): one
 frame per block, one Zstandard block per 32 KiB chunk of the LZ4 encoder's match search, predefined sequence
-tables, no repeat offsets, no checksum; ``level`` is recorded and changes nothing.  ``compress`` raises
+tables, no repeat offsets, no checksum; ``level`` is recorded and changes nothing.  The options word
+(``ENC_TABLES``, ``ENC_REPEAT``; ``ENC_ADAPTIVE`` is both) turns on per-block table modes and repeat-offset codes.  ``compress`` raises
 :class:`lz4.BadCompressionRatioError` when the frame is no smaller than the input; the writer then stores the
 block as type NONE, which ``compress_many_sections`` does.  ``zstd.block_compressor("zstd[:level=N]")`` makes
 one; ``block_codec.block_compressor("zstd")`` is still an unknown compression.
@@ -36,6 +37,9 @@ from .lz4 import (COMPRESSION_TYPE_NONE, MAX_BLOCK, BadCompressionRatioError, En
 
 COMPRESSION_TYPE_ZSTD = 2  # include/dwarfs/compression.h:34-42
 FLAG_SINGLE_SEGMENT, FLAG_CHECKSUM, FLAG_CONTENT_SIZE = 1, 2, 4
+# the encoder's options word: per-block table modes, repeat-offset codes, both
+ENC_TABLES, ENC_REPEAT = N.RPP_ZSTD_ENC_TABLES, N.RPP_ZSTD_ENC_REPEAT
+ENC_ADAPTIVE = ENC_TABLES | ENC_REPEAT
 
 
 class FrameInfo(NamedTuple):
@@ -172,20 +176,20 @@ def bound(n: int) -> int:
     return int(N.lib().rpp_zstd_bound(int(n)))
 
 
-def host_encode(data: bytes):
-    """``rpp_zstd_host_encode``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
+def host_encode(data: bytes, options: int = 0):
+    """``rpp_zstd_host_encode_opt``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
     src = np.frombuffer(bytes(data) + b"\0", np.uint8)
     cap = bound(len(src) - 1)
     out = np.zeros(cap, np.uint8)
     n, flag = C.c_uint64(), C.c_uint32()
-    _raise_status(N.lib().rpp_zstd_host_encode(src.ctypes.data_as(C.c_void_p), len(src) - 1,
-                                               out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(flag)))
+    _raise_status(N.lib().rpp_zstd_host_encode_opt(src.ctypes.data_as(C.c_void_p), len(src) - 1, int(options),
+                                                   out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(flag)))
     return out[:n.value].tobytes(), bool(flag.value)
 
 
 def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
-                 stream: Optional[torch.cuda.Stream] = None) -> EncodedBatch:
-    """One ``rpp_zstd_encode_batch`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
+                 stream: Optional[torch.cuda.Stream] = None, options: int = 0) -> EncodedBatch:
+    """One ``rpp_zstd_encode_batch_opt`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
     tensor; host lists of offsets and sizes): one frame per block; ``flags`` is 1 where size >= input size.
     Asynchronous on the stream."""
     dev = d_in.device
@@ -202,24 +206,28 @@ def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
     status = torch.zeros(n, dtype=torch.int32, device=dev)
     ws_bytes = int(N.lib().rpp_zstd_encode_workspace_bytes(total, n))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    _raise_status(N.lib().rpp_zstd_encode_batch(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, _ptr(out), _ptr(d_ooff),
-                                                _ptr(sizes), _ptr(flags), _ptr(status), total, _ptr(ws), ws_bytes,
-                                                _stream_ptr(stream)))
+    _raise_status(N.lib().rpp_zstd_encode_batch_opt(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, int(options), _ptr(out),
+                                                    _ptr(d_ooff), _ptr(sizes), _ptr(flags), _ptr(status), total,
+                                                    _ptr(ws), ws_bytes, _stream_ptr(stream)))
     return EncodedBatch(out, d_ooff, sizes, flags, status, d_in, d_ioff, d_isz)
 
 
 class ZstdBlockCompressor:
     """``zstd_block_compressor`` (src/compression/zstd.cpp:320-441).  ``level`` (at most 22, ZSTD_maxCLevel) is
-    recorded and does not change the search."""
+    recorded and does not change the search.  ``options`` is the encoder's options word (``ENC_TABLES``,
+    ``ENC_REPEAT``, ``ENC_ADAPTIVE``); 0 writes the bytes pinned in tests/golden/zstd_enc_kat.json."""
 
-    def __init__(self, level: int = 22, device="cuda"):
+    def __init__(self, level: int = 22, device="cuda", options: int = 0):
         if int(level) > 22:
             raise RuntimeError(f"invalid option(s) for zstd: level={level}")
+        if int(options) & ~ENC_ADAPTIVE:
+            raise ValueError(f"unknown zstd encoder options: {options}")
         self.level = int(level)
         self.device = torch.device(device)
+        self.options = int(options)
 
     def clone(self) -> "ZstdBlockCompressor":
-        return ZstdBlockCompressor(self.level, self.device)
+        return ZstdBlockCompressor(self.level, self.device, self.options)
 
     def type(self) -> int:
         return COMPRESSION_TYPE_ZSTD
@@ -238,7 +246,7 @@ class ZstdBlockCompressor:
 
     def _encode(self, blocks: Sequence[bytes]) -> EncodedBatch:
         d_in, offs = _upload(blocks, self.device)
-        return encode_batch(d_in, offs, [len(b) for b in blocks])
+        return encode_batch(d_in, offs, [len(b) for b in blocks], options=self.options)
 
     def compress(self, data: bytes, metadata: Optional[str] = None) -> bytes:
         out = self.compress_many([data], metadata, keep_bad=True)[0]
@@ -253,7 +261,7 @@ class ZstdBlockCompressor:
         if not blocks:
             return []
         if self.device.type == "cpu":  # the host restatement: the kernels' bytes without a GPU
-            frames, flags = zip(*(host_encode(b) for b in blocks))
+            frames, flags = zip(*(host_encode(b, self.options) for b in blocks))
         else:
             res = self._encode(blocks)
             torch.cuda.current_stream().synchronize()

@@ -1028,8 +1028,9 @@ int rpp_lz4_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t ca
  *             two: entropy (one wave per chunk), place (one wave per frame),
  *             emit (one wave per chunk).  The complete definition is at the top
  *             of dwarfs_amd/csrc/zstd_encode_host.cpp.  Not libzstd's bytes; any
- *             Zstandard decoder reads them.  Limits: predefined tables only, no
- *             repeat offsets, 32 KiB blocks, a 64 KiB match window, no
+ *             Zstandard decoder reads them.  Limits: predefined tables only and
+ *             no repeat offsets unless the options word of the *_opt calls
+ *             asks for them, 32 KiB blocks, a 64 KiB match window, no
  *             compression level, no Content_Checksum.  Blocks hold at most
  *             RPP_LZ4_MAX_BLOCK bytes: a longer one gets RPP_INVALID_ARGUMENT
  *             in its status.
@@ -1103,6 +1104,28 @@ int rpp_zstd_encode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, con
  * at least rpp_zstd_bound(n), else RPP_OUTPUT_TOO_SMALL. */
 int rpp_zstd_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
                          uint32_t* bad_ratio);
+
+/*
+ * The encoder's options word.  0 writes the bytes of rpp_zstd_encode_batch and rpp_zstd_host_encode, which
+ * both are the options-0 calls of the functions below.  Any other bit set: RPP_INVALID_ARGUMENT.
+ *   RPP_ZSTD_ENC_TABLES  per block and table (LL, OF, ML) the mode RLE (one code in the block),
+ *                        FSE_Compressed (the block's own distribution, accuracy log 5 or 6, when its
+ *                        description pays for itself by an integer estimate) or Predefined; never Repeat_Mode.
+ *   RPP_ZSTD_ENC_REPEAT  Repeated_Offset1 and Repeated_Offset2 codes for an offset equal to that of one of
+ *                        the two sequences before it in the same 32 KiB chunk; never Repeated_Offset3, and
+ *                        a chunk's first sequence is written in full.
+ * The rules are stated in dwarfs_amd/csrc/zstd_enc_common.h and at the top of zstd_encode_host.cpp.  The
+ * bound (rpp_zstd_bound), the workspace (rpp_zstd_encode_workspace_bytes) and every other part of the
+ * contract are those of the functions above.
+ */
+#define RPP_ZSTD_ENC_TABLES 1u
+#define RPP_ZSTD_ENC_REPEAT 2u
+int rpp_zstd_encode_batch_opt(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                              uint32_t nblocks, uint32_t options, uint8_t* d_out, const uint64_t* d_out_offsets,
+                              uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes,
+                              void* d_workspace, uint64_t workspace_bytes, void* stream);
+int rpp_zstd_host_encode_opt(const uint8_t* in, uint64_t n, uint32_t options, uint8_t* out, uint64_t capacity,
+                             uint64_t* out_bytes, uint32_t* bad_ratio);
 
 #ifdef __cplusplus
 }

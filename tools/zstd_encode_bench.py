@@ -1,6 +1,6 @@
 """Times the Zstandard block encoder on the GPU and writes one JSON line per batch shape.
 
-    python tools/zstd_encode_bench.py [--iters 5] [--out profiles/zstd_encode.jsonl]
+    python tools/zstd_encode_bench.py [--iters 5] [--options 0 3] [--out profiles/zstd_encode.jsonl]
 
 Data: blocks of 1 MiB made by the generators of tests/golden/make_lz4_kat.py and tests/zstd_enc_cases.py (NOT the
 16 MiB blocks mkdwarfs writes), and every test input once.  Every device time is taken with device events around
@@ -9,7 +9,9 @@ GiB/s of input.  "kernels_seconds" holds the mean device time per call of the fi
 entropy, place, emit), taken from a profiler trace of a further `--iters` calls (null where the profiler reports
 no kernels).  "lz4_seconds" is rpp_lz4_encode_batch on the same inputs, in the same run; "frame_bytes" and
 "lz4_bytes" are what the two write.  No speed bar is set: nobody has measured this encoder before, and these
-rows are first measurements, the baseline a tuning change starts from.
+rows are first measurements, the baseline a tuning change starts from.  `--options` lists the encoder's options
+words (rpp_zstd_encode_batch_opt: 1 per-block table modes, 2 repeat offsets, 3 both); every batch is encoded with
+each of them, one row per batch and options word ("options"), and the rows are appended to the file.
 """
 import argparse
 import ctypes as C
@@ -39,6 +41,7 @@ def main():
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--options", type=int, nargs="+", default=[0])
     ap.add_argument("--out", default=str(ROOT / "profiles" / "zstd_encode.jsonl"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "zstd_encode_bench needs a GPU"
@@ -60,10 +63,10 @@ def main():
         d_in, in_offs = _upload(blocks, dev)
         arrays = [S._i64(in_offs, dev), S._i64(sizes, dev)]
         results = {}
-        for codec, bound, ws_of, call_of in (("zstd", Z.bound, N.lib().rpp_zstd_encode_workspace_bytes,
-                                              N.lib().rpp_zstd_encode_batch),
-                                             ("lz4", lz4.bound, N.lib().rpp_lz4_encode_workspace_bytes,
-                                              N.lib().rpp_lz4_encode_batch)):
+        codecs = [(("zstd", o), Z.bound, N.lib().rpp_zstd_encode_workspace_bytes,
+                   lambda *a, o=o: N.lib().rpp_zstd_encode_batch_opt(*a[:4], o, *a[4:])) for o in args.options]
+        codecs.append((("lz4", 0), lz4.bound, N.lib().rpp_lz4_encode_workspace_bytes, N.lib().rpp_lz4_encode_batch))
+        for (codec, options), bound, ws_of, call_of in codecs:
             out_offs, cap = _layout([bound(s) for s in sizes])
             out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
             d_ooff = S._i64(out_offs, dev)
@@ -112,18 +115,20 @@ def main():
                     kernels = found if len(found) == len(KERNELS) else None
                 except Exception as e:  # the trace is an extra: the row stands without it
                     print(f"no kernel trace: {e}", file=sys.stderr)
-            results[codec] = (a.elapsed_time(b) / 1e3 / args.iters, int(out_sizes.sum().item()), ws_bytes, kernels)
+            results[codec, options] = (a.elapsed_time(b) / 1e3 / args.iters, int(out_sizes.sum().item()), ws_bytes, kernels)
             del out, ws
-        (t, frame_bytes, ws_bytes, kernels), (t_lz4, lz4_bytes, _, _) = results["zstd"], results["lz4"]
-        rows.append({"what": "encode", "device": torch.cuda.get_device_name(0), "shape": shape, "blocks": n,
-                     "input_bytes": total, "frame_bytes": frame_bytes, "lz4_bytes": lz4_bytes,
-                     "workspace_bytes": ws_bytes, "iters": args.iters, "seconds": t, "gib_per_s": total / GIB / t,
-                     "kernels_seconds": kernels, "lz4_seconds": t_lz4, "lz4_gib_per_s": total / GIB / t_lz4,
-                     "first_measurement": True})
-        print(json.dumps(rows[-1]), flush=True)
+        t_lz4, lz4_bytes, _, _ = results["lz4", 0]
+        for o in args.options:
+            t, frame_bytes, ws_bytes, kernels = results["zstd", o]
+            rows.append({"what": "encode", "device": torch.cuda.get_device_name(0), "shape": shape, "options": o,
+                         "blocks": n, "input_bytes": total, "frame_bytes": frame_bytes, "lz4_bytes": lz4_bytes,
+                         "workspace_bytes": ws_bytes, "iters": args.iters, "seconds": t, "gib_per_s": total / GIB / t,
+                         "kernels_seconds": kernels, "lz4_seconds": t_lz4, "lz4_gib_per_s": total / GIB / t_lz4,
+                         "first_measurement": True})
+            print(json.dumps(rows[-1]), flush=True)
         del d_in
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "w") as f:
+    with open(args.out, "a") as f:
         for r in rows:
             f.write(json.dumps(r) + "\n")
 
