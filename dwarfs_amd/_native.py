@@ -150,6 +150,10 @@ EXPORTED_SYMBOLS = (
     "rpp_zstd_host_encode",
     "rpp_zstd_encode_batch_opt",
     "rpp_zstd_host_encode_opt",
+    "rpp_lz4_encode_batch_search",
+    "rpp_lz4_host_encode_search",
+    "rpp_zstd_encode_batch_search",
+    "rpp_zstd_host_encode_search",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -158,6 +162,7 @@ RPP_HASH_SHA512_256 = 2
 
 RPP_ZSTD_ENC_TABLES = 1  # the options word of rpp_zstd_encode_batch_opt / rpp_zstd_host_encode_opt
 RPP_ZSTD_ENC_REPEAT = 2
+RPP_SEARCH_LAZY = 0x100  # the search word of the *_search calls: depth (1, 2, 4, 8) | RPP_SEARCH_LAZY
 
 RPP_SIMILARITY_NILSIMSA = 0
 RPP_SIMILARITY_HISTOGRAM = 1
@@ -509,6 +514,14 @@ def lib() -> C.CDLL:
         L.rpp_zstd_encode_batch_opt.restype = C.c_int
         L.rpp_zstd_host_encode_opt.argtypes = [P, U64, U32, P, U64, C.POINTER(U64), C.POINTER(U32)]
         L.rpp_zstd_host_encode_opt.restype = C.c_int
+        L.rpp_lz4_encode_batch_search.argtypes = [P, P, P, U32, U32, P, P, P, P, P, U64, P, U64, P]
+        L.rpp_lz4_encode_batch_search.restype = C.c_int
+        L.rpp_lz4_host_encode_search.argtypes = [P, U64, U32, P, U64, C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_lz4_host_encode_search.restype = C.c_int
+        L.rpp_zstd_encode_batch_search.argtypes = [P, P, P, U32, U32, U32, P, P, P, P, P, U64, P, U64, P]
+        L.rpp_zstd_encode_batch_search.restype = C.c_int
+        L.rpp_zstd_host_encode_search.argtypes = [P, U64, U32, U32, P, U64, C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_zstd_host_encode_search.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

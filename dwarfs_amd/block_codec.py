@@ -356,16 +356,26 @@ class NullBlockCompressor:
 
 def block_compressor(spec: str, device="cuda"):
     """``block_compressor(spec)`` for ``ricepp[:block_size=N]``, ``lz4``, ``lz4hc[:level=N]`` and ``null``
-    (src/compressor_registry.cpp:50-59)."""
+    (src/compressor_registry.cpp:50-59).  ``lz4`` and ``lz4hc`` also take ``depth=N`` (1, 2, 4, 8) and
+    ``lazy=0|1``, which make the encoder's search word (``lz4hc:level=9:depth=8:lazy=1``); ``level`` maps to no
+    search."""
     name, _, opts = spec.partition(":")
     if name in ("lz4", "lz4hc", "null"):
-        level = 9 if name == "lz4hc" else None  # lz4.cpp's default level
-        for kv in filter(None, opts.split(",")):
-            k, eq, v = kv.partition("=")
-            if name != "lz4hc" or k != "level" or not eq or not v.isdigit() or int(v) > 12:
+        level = [9 if name == "lz4hc" else None]  # lz4.cpp's default level
+
+        def take_level(k, v):
+            if name != "lz4hc" or k != "level" or not v.isdigit() or int(v) > 12:
+                return False
+            level[0] = int(v)
+            return True
+
+        kvs = [kv for kv in opts.replace(",", ":").split(":") if kv]
+        if name == "null":
+            for kv in kvs:
                 raise RuntimeError(f"invalid option(s) for {name}: {kv}")
-            level = int(v)
-        return NullBlockCompressor() if name == "null" else Z.Lz4BlockCompressor(level, device)
+            return NullBlockCompressor()
+        search = Z.spec_search(kvs, name, take_level)
+        return Z.Lz4BlockCompressor(level[0], device, search)
     if name != "ricepp":
         raise RuntimeError(f"unknown compression: {name}")
     bs = 128

@@ -25,6 +25,20 @@ constexpr uint32_t kSeqsPerChunk = kChunk / kMinMatch;
 
 RPP_LZ4_HD inline uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashBits); }
 
+// The search word (defined at the top of lz4_host.cpp): 0 is the one-candidate greedy search; else
+// depth | kSearchLazy with a depth of 1, 2, 4 or 8 candidates per hash value.
+constexpr uint32_t kSearchLazy = 0x100;
+constexpr uint32_t kMaxDepth = 8;
+// A candidate's score is its common prefix up to this many bytes: one cache line, and one turn of the whole-wave
+// compare that extends the match taken.  Two candidates that both agree this far are told apart by position
+// alone, and a match this long is never given up for the next position's: a byte more would gain under 2 %.
+constexpr uint32_t kDeepCap = 64;
+
+RPP_LZ4_HD inline bool search_valid(uint32_t search) {
+  const uint32_t d = search & ~kSearchLazy;
+  return search == 0 || d == 1 || d == 2 || d == 4 || d == 8;
+}
+
 // extension bytes behind a token nibble that stands for `v` (a literal length, or a match length - 4)
 RPP_LZ4_HD inline uint32_t ext_bytes(uint32_t v) { return v >= 15 ? (v - 15) / 255 + 1 : 0; }
 

@@ -29,6 +29,30 @@
 //     its length is the common prefix, cut at min(chunk end, n - 5).
 //   * the sequences of all chunks, in order, are one LZ4 block: a literal run
 //     that spans a chunk boundary belongs to the next match, wherever it is.
+//
+// The search word (find_sequences with `search`, the *_search entry points):
+// depth | RPP_SEARCH_LAZY with a depth of 1, 2, 4 or 8; 0 is the definition
+// above and any other word an invalid argument.  Chunks, the table's start
+// (the kChunk bytes before the chunk), steps (every lookup before the step's
+// inserts, a covered step skipped whole, its positions never inserted), hash4,
+// the conditions on a match and the cut of a length stay as above, with
+// last_start = n - 12 and lim_end = min(chunk end, n - 5).  Four things change:
+//   * bucket: a hash value holds the `depth` highest positions inserted so far.
+//   * score: a position p with p <= last_start and p + 4 <= lim_end scores
+//     every candidate c of its bucket that holds the same 4 bytes at
+//     p - c <= 65535: min(common prefix cut at lim_end, kDeepCap).  best(p) is
+//     the candidate with the highest score, of equal scores the highest
+//     position (the smallest offset).
+//   * choice: without LAZY the first position at or behind the cursor that has
+//     a best is taken.  With LAZY a position p is passed over (it becomes a
+//     literal) when p + 1 lies in the same step and has a best whose score is
+//     strictly greater; the position taken is the first one at or behind the
+//     cursor that has a best and is not passed over.  A step's last position
+//     is never passed over, nor is a score of kDeepCap.
+//   * length: the match taken is (p, best(p)) with the full common prefix, cut
+//     at lim_end; the cursor moves to its end and the step goes on.
+// Depth 1 without LAZY gives the sequences of search 0.  `level` maps to no
+// word: that table needs timings first.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -70,6 +94,59 @@ void rpp_lz4::find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& se
         if (p > last_start || p + 4 > lim_end || p - c > kMaxOffset || rd32(in + c) != rd32(in + p)) continue;
         const uint32_t lim = lim_end - p;
         uint32_t len = 4;
+        while (len < lim && in[c + len] == in[p + len]) ++len;
+        seqs.push_back({p, len, p - c});
+        cursor = p + len;
+        p = cursor - 1;
+      }
+    }
+  }
+}
+
+void rpp_lz4::find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& seqs, uint32_t search) {
+  if (search == 0) return find_sequences(in, n, seqs);
+  if (n < kMatchStartGap + 1) return;
+  const uint32_t depth = search & ~kSearchLazy;
+  const bool lazy = search & kSearchLazy;
+  const uint32_t last_start = n - kMatchStartGap, match_end = n - kLastLiterals;
+  std::vector<uint32_t> tab(size_t(depth) << kHashBits);  // per hash value: position + 1, highest first; 0: empty
+  auto insert = [&](uint32_t q) {
+    uint32_t* const b = tab.data() + size_t(hash4(rd32(in + q))) * depth;
+    for (uint32_t k = depth - 1; k > 0; --k) b[k] = b[k - 1];
+    b[0] = q + 1;
+  };
+  for (uint32_t cs = 0; cs < n; cs += kChunk) {
+    const uint32_t ce = std::min(cs + kChunk, n), lim_end = std::min(ce, match_end);
+    std::fill(tab.begin(), tab.end(), 0u);
+    for (uint32_t q = cs >= kChunk ? cs - kChunk : 0; q < cs; ++q)
+      if (q + 4 <= n) insert(q);
+    uint32_t cursor = cs;  // the end of the chunk's last match
+    for (uint32_t ss = cs; ss < ce; ss += kStep) {
+      const uint32_t se = std::min(ss + kStep, ce);
+      if (cursor >= se) continue;
+      uint32_t best[kStep], score[kStep];  // best: candidate + 1; 0: none
+      for (uint32_t p = ss; p < se; ++p) {
+        uint32_t& bc = best[p - ss] = 0;
+        uint32_t& bs = score[p - ss] = 0;
+        if (p > last_start || p + 4 > lim_end) continue;
+        const uint32_t word = rd32(in + p), lim = std::min(lim_end - p, kDeepCap);
+        const uint32_t* const b = tab.data() + size_t(hash4(word)) * depth;
+        for (uint32_t k = 0; k < depth && b[k]; ++k) {
+          const uint32_t c = b[k] - 1;
+          if (p - c > kMaxOffset || rd32(in + c) != word) continue;
+          uint32_t s = 4;
+          while (s < lim && in[c + s] == in[p + s]) ++s;
+          if (s > bs) bs = s, bc = c + 1;
+        }
+      }
+      for (uint32_t p = ss; p < se; ++p)
+        if (p + 4 <= n) insert(p);
+      for (uint32_t p = std::max(cursor, ss); p < se; ++p) {
+        const uint32_t i = p - ss;
+        if (!best[i]) continue;
+        if (lazy && p + 1 < se && best[i + 1] && score[i + 1] > score[i]) continue;
+        const uint32_t c = best[i] - 1, lim = lim_end - p;
+        uint32_t len = score[i];
         while (len < lim && in[c + len] == in[p + len]) ++len;
         seqs.push_back({p, len, p - c});
         cursor = p + len;
@@ -144,11 +221,18 @@ extern "C" int rpp_lz4_host_decode(const uint8_t* in, uint64_t in_bytes, uint8_t
 
 extern "C" int rpp_lz4_host_encode(const uint8_t* in, uint64_t n, uint8_t* out, uint64_t capacity,
                                    uint64_t* out_bytes, uint32_t* bad_ratio) {
-  if ((n && !in) || !out || !out_bytes) return RPP_INVALID_ARGUMENT;
+  return rpp_lz4_host_encode_search(in, n, 0, out, capacity, out_bytes, bad_ratio);
+}
+
+static_assert(RPP_SEARCH_LAZY == rpp_lz4::kSearchLazy, "the search word");
+
+extern "C" int rpp_lz4_host_encode_search(const uint8_t* in, uint64_t n, uint32_t search, uint8_t* out,
+                                          uint64_t capacity, uint64_t* out_bytes, uint32_t* bad_ratio) {
+  if ((n && !in) || !out || !out_bytes || !search_valid(search)) return RPP_INVALID_ARGUMENT;
   if (n > kMaxBlock) return RPP_INVALID_ARGUMENT;
   if (capacity < rpp_lz4_bound(n)) return RPP_OUTPUT_TOO_SMALL;
   std::vector<Seq> seqs;
-  find_sequences(in, uint32_t(n), seqs);
+  find_sequences(in, uint32_t(n), seqs, search);
   uint8_t* o = out;
   uint32_t anchor = 0;
   for (const Seq& s : seqs) {

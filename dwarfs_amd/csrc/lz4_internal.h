@@ -18,6 +18,8 @@ struct Seq {  // a match of `len` bytes at `pos`, `off` bytes back
 
 // the sequences of a block of n bytes, in order (host memory)
 void find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& seqs);
+// ... under a search word (valid by search_valid; 0 is the call above)
+void find_sequences(const uint8_t* in, uint32_t n, std::vector<Seq>& seqs, uint32_t search);
 
 // the kernels' side: for translation units that have included <hip/hip_runtime.h> and say so
 #if defined(RPP_LZ4_KERNEL_SIDE)
@@ -46,6 +48,14 @@ EncodeWs carve_workspace(void* d_workspace, uint64_t total_bytes, uint32_t nbloc
 // counts, and every chunk's sequence list.
 void launch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes, uint32_t nblocks,
                    const EncodeWs& ws, uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status, void* stream);
+// ... under a search word (valid by search_valid): 0 is the call above, any other word runs
+// rpp_lz4_deep_search_kernel (lz4_search_deep.hip) in the search kernel's place.
+void launch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes, uint32_t nblocks,
+                   const EncodeWs& ws, uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status, uint32_t search,
+                   void* stream);
+// the deep search kernel alone, behind the prep kernel on `stream` (search != 0)
+void launch_deep_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                        uint32_t nblocks, const EncodeWs& ws, uint32_t search, void* stream);
 
 // the block of global chunk g: the last b with chunk_base[b] <= g
 __device__ inline uint32_t block_of_chunk(const uint32_t* chunk_base, uint32_t nblocks, uint32_t g) {

@@ -423,6 +423,16 @@ void rpp_lz4::launch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, c
                      nblocks, ws);
 }
 
+void rpp_lz4::launch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                            uint32_t nblocks, const EncodeWs& ws, uint64_t* d_out_bytes, uint32_t* d_flags,
+                            int32_t* d_status, uint32_t search, void* stream) {
+  if (search == 0)
+    return launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, stream);
+  hipLaunchKernelGGL(rpp_lz4_prep_kernel, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), d_in_bytes,
+                     nblocks, ws, d_out_bytes, d_flags, d_status);
+  launch_deep_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, search, stream);
+}
+
 extern "C" int rpp_lz4_decode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
                                     uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets,
                                     const uint64_t* d_out_bytes, int32_t* d_status, void* stream) {
@@ -445,6 +455,18 @@ extern "C" int rpp_lz4_encode_batch(const uint8_t* d_in, const uint64_t* d_in_of
                                     uint32_t nblocks, uint8_t* d_out, const uint64_t* d_out_offsets,
                                     uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes,
                                     void* d_workspace, uint64_t workspace_bytes, void* stream) {
+  return rpp_lz4_encode_batch_search(d_in, d_in_offsets, d_in_bytes, nblocks, 0, d_out, d_out_offsets, d_out_bytes,
+                                     d_flags, d_status, total_bytes, d_workspace, workspace_bytes, stream);
+}
+
+static_assert(RPP_SEARCH_LAZY == kSearchLazy, "the search word");
+
+extern "C" int rpp_lz4_encode_batch_search(const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                           const uint64_t* d_in_bytes, uint32_t nblocks, uint32_t search,
+                                           uint8_t* d_out, const uint64_t* d_out_offsets, uint64_t* d_out_bytes,
+                                           uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes,
+                                           void* d_workspace, uint64_t workspace_bytes, void* stream) {
+  if (!search_valid(search)) return RPP_INVALID_ARGUMENT;
   if (nblocks == 0) return RPP_OK;
   if (!d_in || !d_in_offsets || !d_in_bytes || !d_out || !d_out_offsets || !d_out_bytes || !d_flags || !d_status ||
       !d_workspace || ((uintptr_t)d_workspace & 15))
@@ -453,7 +475,7 @@ extern "C" int rpp_lz4_encode_batch(const uint8_t* d_in, const uint64_t* d_in_of
   if (mc >= 0x7fffffffu) return RPP_INVALID_ARGUMENT;
   if (workspace_bytes < rpp_lz4_encode_workspace_bytes(total_bytes, nblocks)) return RPP_OUTPUT_TOO_SMALL;
   const EncodeWs ws = carve_workspace(d_workspace, total_bytes, nblocks);
-  launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, stream);
+  launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(rpp_lz4_place_kernel, dim3(nblocks), dim3(kWave), 0, s, d_in_bytes, nblocks, ws, d_out,
                      d_out_offsets, d_out_bytes, d_flags, d_status);

@@ -565,7 +565,17 @@ extern "C" int rpp_zstd_encode_batch_opt(const uint8_t* d_in, const uint64_t* d_
                                          const uint64_t* d_out_offsets, uint64_t* d_out_bytes, uint32_t* d_flags,
                                          int32_t* d_status, uint64_t total_bytes, void* d_workspace,
                                          uint64_t workspace_bytes, void* stream) {
-  if (options & ~kEncOptionsMask) return RPP_INVALID_ARGUMENT;
+  return rpp_zstd_encode_batch_search(d_in, d_in_offsets, d_in_bytes, nblocks, options, 0, d_out, d_out_offsets,
+                                      d_out_bytes, d_flags, d_status, total_bytes, d_workspace, workspace_bytes, stream);
+}
+
+extern "C" int rpp_zstd_encode_batch_search(const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                            const uint64_t* d_in_bytes, uint32_t nblocks, uint32_t options,
+                                            uint32_t search, uint8_t* d_out, const uint64_t* d_out_offsets,
+                                            uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status,
+                                            uint64_t total_bytes, void* d_workspace, uint64_t workspace_bytes,
+                                            void* stream) {
+  if ((options & ~kEncOptionsMask) || !rpp_lz4::search_valid(search)) return RPP_INVALID_ARGUMENT;
   if (nblocks == 0) return RPP_OK;
   if (!d_in || !d_in_offsets || !d_in_bytes || !d_out || !d_out_offsets || !d_out_bytes || !d_flags || !d_status ||
       !d_workspace || ((uintptr_t)d_workspace & 15))
@@ -587,7 +597,7 @@ extern "C" int rpp_zstd_encode_batch_opt(const uint8_t* d_in, const uint64_t* d_
   zws.size = reinterpret_cast<uint32_t*>(p);
   p += align16(4 * mc);
   zws.at = reinterpret_cast<uint32_t*>(p);
-  rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, stream);
+  rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (options)
     hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<true>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,

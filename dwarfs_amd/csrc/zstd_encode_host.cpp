@@ -95,8 +95,12 @@
 //              OF, ML order (fse_write_description; RLE: the code), bitstream;
 //              the chains as above in the block's tables, the first states
 //              written in their tables' logs (RLE: 0 bits).
+// The search word (rpp_zstd_host_encode_search, rpp_zstd_encode_batch_search)
+// changes the sequences alone: the LZ4 encoder's deeper search, defined at the
+// top of lz4_host.cpp.  0 is the search above; the options word applies to
+// whatever sequences the search hands over.
 // The block rule (Compressed only when strictly smaller than the chunk) and so
-// rpp_zstd_bound are the same for every options word.
+// rpp_zstd_bound are the same for every options word and every search word.
 // The ratio flag is size >= n (zstd_block_compressor::compress's
 // bad_compression_ratio_error, src/compression/zstd.cpp:435).
 #include <algorithm>
@@ -282,12 +286,19 @@ extern "C" int rpp_zstd_host_encode(const uint8_t* in, uint64_t n, uint8_t* out,
 
 extern "C" int rpp_zstd_host_encode_opt(const uint8_t* in, uint64_t n, uint32_t options, uint8_t* out,
                                         uint64_t capacity, uint64_t* out_bytes, uint32_t* bad_ratio) {
-  if ((n && !in) || !out || !out_bytes || (options & ~kEncOptionsMask)) return RPP_INVALID_ARGUMENT;
+  return rpp_zstd_host_encode_search(in, n, options, 0, out, capacity, out_bytes, bad_ratio);
+}
+
+extern "C" int rpp_zstd_host_encode_search(const uint8_t* in, uint64_t n, uint32_t options, uint32_t search,
+                                           uint8_t* out, uint64_t capacity, uint64_t* out_bytes,
+                                           uint32_t* bad_ratio) {
+  if ((n && !in) || !out || !out_bytes || (options & ~kEncOptionsMask) || !rpp_lz4::search_valid(search))
+    return RPP_INVALID_ARGUMENT;
   if (n > rpp_lz4::kMaxBlock) return RPP_INVALID_ARGUMENT;
   if (capacity < encode_bound(n)) return RPP_OUTPUT_TOO_SMALL;
   static const Tables tables;
   std::vector<rpp_lz4::Seq> seqs;
-  rpp_lz4::find_sequences(in, uint32_t(n), seqs);
+  rpp_lz4::find_sequences(in, uint32_t(n), seqs, search);
   uint8_t* o = out + frame_header(n, out);
   if (n == 0) {
     block_header(o, true, kRaw, 0);

@@ -15,8 +15,11 @@ does.
 ``device="cpu"`` runs the host restatement of the kernels (rpp_lz4_host_encode / rpp_lz4_host_decode), which
 writes the same bytes; the section helpers need the GPU.
 
-One encoder serves both names: ``lz4hc:level=N`` records the level (0..12) and changes nothing in the search
-yet.  Besides the one-block API there are ``compress_many`` / ``decompress_many``: one launch for a batch.
+One encoder serves both names: ``lz4hc:level=N`` records the level (0..12) and maps to no search: what changes
+the search is the search word (``search=``, or ``depth=N`` and ``lazy=0|1`` in a spec), ``depth | SEARCH_LAZY``
+with a depth of 1, 2, 4 or 8 candidates per hash value; 0, the default, is the one-candidate greedy search
+(defined at the top of csrc/lz4_host.cpp).  Besides the one-block API there are ``compress_many`` /
+``decompress_many``: one launch for a batch.
 """
 
 from __future__ import annotations
@@ -37,6 +40,7 @@ COMPRESSION_TYPE_LZ4 = 3
 COMPRESSION_TYPE_LZ4HC = 4
 MAX_BLOCK = 1 << 30  # RPP_LZ4_MAX_BLOCK
 FRAME_BYTES = 4
+SEARCH_LAZY = N.RPP_SEARCH_LAZY  # the search word: depth (1, 2, 4 or 8) | SEARCH_LAZY; 0: the one-candidate search
 
 
 class BadCompressionRatioError(RuntimeError):
@@ -78,14 +82,40 @@ def host_decode(block: bytes, size: int):
     return int(st), out[:size].tobytes()
 
 
-def host_encode(data: bytes):
-    """``rpp_lz4_host_encode``: (the LZ4 block, the ratio flag): the bytes the kernels write, on the CPU."""
+def check_search(search: int) -> int:
+    """The search word ``depth | SEARCH_LAZY`` (depth 1, 2, 4 or 8), or 0: anything else raises ValueError."""
+    search = int(search)
+    if search != 0 and (search & ~SEARCH_LAZY) not in (1, 2, 4, 8):
+        raise ValueError(f"unknown search word: {search}")
+    return search
+
+
+def spec_search(opts: Sequence[str], name: str, other=lambda key, value: False) -> int:
+    """The search word of a spec's options ``depth=N`` (1, 2, 4, 8) and ``lazy=0|1`` (lazy alone: depth 1); an
+    option that is neither and that ``other(key, value)`` does not take raises ``invalid option(s) for ...``."""
+    depth, lazy, bad = 0, 0, []
+    for opt in opts:
+        key, eq, value = opt.partition("=")
+        if key == "depth" and eq and value in ("1", "2", "4", "8"):
+            depth = int(value)
+        elif key == "lazy" and eq and value in ("0", "1"):
+            lazy = int(value)
+        elif not (eq and other(key, value)):
+            bad.append(opt)
+    if bad:
+        raise RuntimeError(f"invalid option(s) for {name}: " + ", ".join(bad))
+    return (depth or 1) | SEARCH_LAZY if lazy else depth
+
+
+def host_encode(data: bytes, search: int = 0):
+    """``rpp_lz4_host_encode_search``: (the LZ4 block, the ratio flag): the bytes the kernels write, on the
+    CPU."""
     src = np.frombuffer(bytes(data), np.uint8)
     cap = bound(len(src))
     out = np.zeros(cap, np.uint8)
     n, flag = C.c_uint64(), C.c_uint32()
-    _raise_status(N.lib().rpp_lz4_host_encode(src.ctypes.data_as(C.c_void_p), len(src), out.ctypes.data_as(C.c_void_p),
-                                              cap, C.byref(n), C.byref(flag)))
+    _raise_status(N.lib().rpp_lz4_host_encode_search(src.ctypes.data_as(C.c_void_p), len(src), int(search),
+                                                     out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(flag)))
     return out[:n.value].tobytes(), bool(flag.value)
 
 
@@ -117,8 +147,8 @@ class EncodedBatch:
 
 
 def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
-                 stream: Optional[torch.cuda.Stream] = None) -> EncodedBatch:
-    """One ``rpp_lz4_encode_batch`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
+                 stream: Optional[torch.cuda.Stream] = None, search: int = 0) -> EncodedBatch:
+    """One ``rpp_lz4_encode_batch_search`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
     tensor; host lists of offsets and sizes).  Asynchronous on the stream."""
     dev = d_in.device
     n = len(in_sizes)
@@ -134,9 +164,9 @@ def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
     status = torch.zeros(n, dtype=torch.int32, device=dev)
     ws_bytes = int(N.lib().rpp_lz4_encode_workspace_bytes(total, n))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    _raise_status(N.lib().rpp_lz4_encode_batch(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, _ptr(out), _ptr(d_ooff),
-                                               _ptr(sizes), _ptr(flags), _ptr(status), total, _ptr(ws), ws_bytes,
-                                               _stream_ptr(stream)))
+    _raise_status(N.lib().rpp_lz4_encode_batch_search(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, int(search), _ptr(out),
+                                                      _ptr(d_ooff), _ptr(sizes), _ptr(flags), _ptr(status), total,
+                                                      _ptr(ws), ws_bytes, _stream_ptr(stream)))
     return EncodedBatch(out, d_ooff, sizes, flags, status, d_in, d_ioff, d_isz)
 
 
@@ -171,16 +201,18 @@ def _upload(blocks: Sequence[bytes], device):
 
 class Lz4BlockCompressor:
     """``lz4_block_compressor`` (src/compression/lz4.cpp:60-117): ``level`` None is ``lz4``, a number
-    ``lz4hc:level=N``."""
+    ``lz4hc:level=N``; the level maps to no search.  ``search`` is the search word (``depth | SEARCH_LAZY``); 0
+    writes the bytes of the one-candidate search."""
 
-    def __init__(self, level: Optional[int] = None, device="cuda"):
+    def __init__(self, level: Optional[int] = None, device="cuda", search: int = 0):
         if level is not None and not 0 <= int(level) <= 12:
             raise RuntimeError(f"invalid option(s) for lz4hc: level={level}")
         self.level = None if level is None else int(level)
         self.device = torch.device(device)
+        self.search = check_search(search)
 
     def clone(self) -> "Lz4BlockCompressor":
-        return Lz4BlockCompressor(self.level, self.device)
+        return Lz4BlockCompressor(self.level, self.device, self.search)
 
     def type(self) -> int:
         return COMPRESSION_TYPE_LZ4 if self.level is None else COMPRESSION_TYPE_LZ4HC
@@ -199,7 +231,7 @@ class Lz4BlockCompressor:
 
     def _encode(self, blocks: Sequence[bytes]) -> EncodedBatch:
         d_in, offs = _upload(blocks, self.device)
-        return encode_batch(d_in, offs, [len(b) for b in blocks])
+        return encode_batch(d_in, offs, [len(b) for b in blocks], search=self.search)
 
     def compress(self, data: bytes, metadata: Optional[str] = None) -> bytes:
         out = self.compress_many([data], metadata, keep_bad=True)[0]
@@ -214,7 +246,7 @@ class Lz4BlockCompressor:
         if not blocks:
             return []
         if self.device.type == "cpu":  # the host restatement: the kernels' bytes without a GPU
-            streams, flags = zip(*(host_encode(b) for b in blocks))
+            streams, flags = zip(*(host_encode(b, self.search) for b in blocks))
         else:
             res = self._encode(blocks)
             torch.cuda.current_stream().synchronize()

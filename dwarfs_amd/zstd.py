@@ -10,7 +10,9 @@ that cannot be parsed ``ZSTD content size error``; a failed decode raises
 
 The encoder is this project's own and deterministic (defined at the top of csrc/zstd_encode_host.cpp): one
 frame per block, one Zstandard block per 32 KiB chunk of the LZ4 encoder's match search, predefined sequence
-tables, no repeat offsets, no checksum; ``level`` is recorded and changes nothing.  The options word
+tables, no repeat offsets, no checksum; ``level`` is recorded and changes nothing (it maps to no search word).  The
+search word (``search=``, or ``depth=N`` and ``lazy=0|1`` in a spec; ``depth | SEARCH_LAZY``, see lz4.py) turns on the
+LZ4 encoder's deeper match search; 0, the default, is the one-candidate greedy search.  The options word
 (``ENC_TABLES``, ``ENC_REPEAT``; ``ENC_ADAPTIVE`` is both) turns on per-block table modes and repeat-offset codes.  ``compress`` raises
 :class:`lz4.BadCompressionRatioError` when the frame is no smaller than the input; the writer then stores the
 block as type NONE, which ``compress_many_sections`` does.  ``zstd.block_compressor("zstd[:level=N]")`` makes
@@ -32,8 +34,8 @@ import torch
 from . import _native as N
 from . import section as S
 from .codec import _raise_status, _stream_ptr
-from .lz4 import (COMPRESSION_TYPE_NONE, MAX_BLOCK, BadCompressionRatioError, EncodedBatch, _layout, _ptr,
-                  _upload)
+from .lz4 import (COMPRESSION_TYPE_NONE, MAX_BLOCK, SEARCH_LAZY, BadCompressionRatioError, EncodedBatch, _layout,
+                  _ptr, _upload, check_search, spec_search)
 
 COMPRESSION_TYPE_ZSTD = 2  # include/dwarfs/compression.h:34-42
 FLAG_SINGLE_SEGMENT, FLAG_CHECKSUM, FLAG_CONTENT_SIZE = 1, 2, 4
@@ -176,20 +178,21 @@ def bound(n: int) -> int:
     return int(N.lib().rpp_zstd_bound(int(n)))
 
 
-def host_encode(data: bytes, options: int = 0):
-    """``rpp_zstd_host_encode_opt``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
+def host_encode(data: bytes, options: int = 0, search: int = 0):
+    """``rpp_zstd_host_encode_search``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
     src = np.frombuffer(bytes(data) + b"\0", np.uint8)
     cap = bound(len(src) - 1)
     out = np.zeros(cap, np.uint8)
     n, flag = C.c_uint64(), C.c_uint32()
-    _raise_status(N.lib().rpp_zstd_host_encode_opt(src.ctypes.data_as(C.c_void_p), len(src) - 1, int(options),
-                                                   out.ctypes.data_as(C.c_void_p), cap, C.byref(n), C.byref(flag)))
+    _raise_status(N.lib().rpp_zstd_host_encode_search(src.ctypes.data_as(C.c_void_p), len(src) - 1, int(options),
+                                                      int(search), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
+                                                      C.byref(flag)))
     return out[:n.value].tobytes(), bool(flag.value)
 
 
 def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
-                 stream: Optional[torch.cuda.Stream] = None, options: int = 0) -> EncodedBatch:
-    """One ``rpp_zstd_encode_batch_opt`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
+                 stream: Optional[torch.cuda.Stream] = None, options: int = 0, search: int = 0) -> EncodedBatch:
+    """One ``rpp_zstd_encode_batch_search`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
     tensor; host lists of offsets and sizes): one frame per block; ``flags`` is 1 where size >= input size.
     Asynchronous on the stream."""
     dev = d_in.device
@@ -206,18 +209,19 @@ def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
     status = torch.zeros(n, dtype=torch.int32, device=dev)
     ws_bytes = int(N.lib().rpp_zstd_encode_workspace_bytes(total, n))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    _raise_status(N.lib().rpp_zstd_encode_batch_opt(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, int(options), _ptr(out),
-                                                    _ptr(d_ooff), _ptr(sizes), _ptr(flags), _ptr(status), total,
-                                                    _ptr(ws), ws_bytes, _stream_ptr(stream)))
+    _raise_status(N.lib().rpp_zstd_encode_batch_search(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, int(options),
+                                                       int(search), _ptr(out), _ptr(d_ooff), _ptr(sizes), _ptr(flags),
+                                                       _ptr(status), total, _ptr(ws), ws_bytes, _stream_ptr(stream)))
     return EncodedBatch(out, d_ooff, sizes, flags, status, d_in, d_ioff, d_isz)
 
 
 class ZstdBlockCompressor:
     """``zstd_block_compressor`` (src/compression/zstd.cpp:320-441).  ``level`` (at most 22, ZSTD_maxCLevel) is
     recorded and does not change the search.  ``options`` is the encoder's options word (``ENC_TABLES``,
-    ``ENC_REPEAT``, ``ENC_ADAPTIVE``); 0 writes the bytes pinned in tests/golden/zstd_enc_kat.json."""
+    ``ENC_REPEAT``, ``ENC_ADAPTIVE``), ``search`` the search word (``depth | SEARCH_LAZY``); 0 and 0 write the bytes
+    pinned in tests/golden/zstd_enc_kat.json."""
 
-    def __init__(self, level: int = 22, device="cuda", options: int = 0):
+    def __init__(self, level: int = 22, device="cuda", options: int = 0, search: int = 0):
         if int(level) > 22:
             raise RuntimeError(f"invalid option(s) for zstd: level={level}")
         if int(options) & ~ENC_ADAPTIVE:
@@ -225,9 +229,10 @@ class ZstdBlockCompressor:
         self.level = int(level)
         self.device = torch.device(device)
         self.options = int(options)
+        self.search = check_search(search)
 
     def clone(self) -> "ZstdBlockCompressor":
-        return ZstdBlockCompressor(self.level, self.device, self.options)
+        return ZstdBlockCompressor(self.level, self.device, self.options, self.search)
 
     def type(self) -> int:
         return COMPRESSION_TYPE_ZSTD
@@ -246,7 +251,7 @@ class ZstdBlockCompressor:
 
     def _encode(self, blocks: Sequence[bytes]) -> EncodedBatch:
         d_in, offs = _upload(blocks, self.device)
-        return encode_batch(d_in, offs, [len(b) for b in blocks], options=self.options)
+        return encode_batch(d_in, offs, [len(b) for b in blocks], options=self.options, search=self.search)
 
     def compress(self, data: bytes, metadata: Optional[str] = None) -> bytes:
         out = self.compress_many([data], metadata, keep_bad=True)[0]
@@ -261,7 +266,7 @@ class ZstdBlockCompressor:
         if not blocks:
             return []
         if self.device.type == "cpu":  # the host restatement: the kernels' bytes without a GPU
-            frames, flags = zip(*(host_encode(b, self.options) for b in blocks))
+            frames, flags = zip(*(host_encode(b, self.options, self.search) for b in blocks))
         else:
             res = self._encode(blocks)
             torch.cuda.current_stream().synchronize()
@@ -306,19 +311,21 @@ class ZstdBlockCompressor:
 
 
 def block_compressor(spec: str, device="cuda") -> ZstdBlockCompressor:
-    """The factory for ``zstd[:level=N]``; any other option raises ``invalid option(s) for zstd: ...``."""
+    """The factory for ``zstd[:level=N][:depth=N][:lazy=0|1]``; any other option raises ``invalid option(s) for
+    zstd: ...``.  ``depth`` and ``lazy`` make the search word; ``level`` maps to none."""
     name, *opts = spec.split(":")
     if name != "zstd":
         raise RuntimeError(f"unknown compression: {name}")
-    level, bad = 22, []
-    for opt in opts:
-        key, _, value = opt.partition("=")
+    level = [22]
+
+    def take_level(key, value):
         try:
             if key != "level" or int(value) > 22:
-                raise ValueError
-            level = int(value)
+                return False
         except ValueError:
-            bad.append(opt)
-    if bad:
-        raise RuntimeError("invalid option(s) for zstd: " + ", ".join(bad))
-    return ZstdBlockCompressor(level, device)
+            return False
+        level[0] = int(value)
+        return True
+
+    search = spec_search(opts, "zstd", take_level)
+    return ZstdBlockCompressor(level[0], device, search=search)

@@ -1127,6 +1127,34 @@ int rpp_zstd_encode_batch_opt(const uint8_t* d_in, const uint64_t* d_in_offsets,
 int rpp_zstd_host_encode_opt(const uint8_t* in, uint64_t n, uint32_t options, uint8_t* out, uint64_t capacity,
                              uint64_t* out_bytes, uint32_t* bad_ratio);
 
+/*
+ * The search word of the LZ4 and Zstandard encoders: depth | RPP_SEARCH_LAZY, depth 1, 2, 4 or 8.  0 is the
+ * search of the calls above (one candidate per hash value, the first position that matches), which are the
+ * search-0 calls of the functions below; any other word is RPP_INVALID_ARGUMENT.
+ *   depth            a hash value keeps its `depth` highest positions; a position scores each of them (the
+ *                    common prefix, up to 64 bytes) and matches the best one, of equals the nearest.
+ *   RPP_SEARCH_LAZY  a position is passed over when the next position of the same 64-position step scores
+ *                    strictly higher.
+ * Depth 1 without RPP_SEARCH_LAZY writes the bytes of search 0 (from another kernel).  The complete definition
+ * is at the top of dwarfs_amd/csrc/lz4_host.cpp.  The match window stays 64 KiB, candidates come from earlier
+ * steps only, and no compression level maps to a word.  Bounds, workspaces, flags, statuses and every other
+ * part of the contracts are those of rpp_lz4_encode_batch, rpp_zstd_encode_batch_opt and the host calls.
+ */
+#define RPP_SEARCH_LAZY 0x100u
+int rpp_lz4_encode_batch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                                uint32_t nblocks, uint32_t search, uint8_t* d_out, const uint64_t* d_out_offsets,
+                                uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes,
+                                void* d_workspace, uint64_t workspace_bytes, void* stream);
+int rpp_lz4_host_encode_search(const uint8_t* in, uint64_t n, uint32_t search, uint8_t* out, uint64_t capacity,
+                               uint64_t* out_bytes, uint32_t* bad_ratio);
+int rpp_zstd_encode_batch_search(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                                 uint32_t nblocks, uint32_t options, uint32_t search, uint8_t* d_out,
+                                 const uint64_t* d_out_offsets, uint64_t* d_out_bytes, uint32_t* d_flags,
+                                 int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                 uint64_t workspace_bytes, void* stream);
+int rpp_zstd_host_encode_search(const uint8_t* in, uint64_t n, uint32_t options, uint32_t search, uint8_t* out,
+                                uint64_t capacity, uint64_t* out_bytes, uint32_t* bad_ratio);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,10 @@
+#!/bin/bash
+# Host-only sanitizer build of the host encoders under the search word: the match search (lz4_host.cpp), the
+# Zstandard encoder (zstd_encode_host.cpp), the decoder (zstd_host.cpp) and search_test.cpp (which has the main),
+# with AddressSanitizer + UndefinedBehaviorSanitizer.
+set -e
+cd "$(dirname "$0")/../.."
+mkdir -p tests/cpp/build
+SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1"
+g++ -std=c++20 $SAN -Wall -Wextra -Iinclude -Idwarfs_amd/csrc dwarfs_amd/csrc/lz4_host.cpp dwarfs_amd/csrc/zstd_host.cpp \
+  dwarfs_amd/csrc/zstd_encode_host.cpp tests/cpp/search_test.cpp -o tests/cpp/build/search_test

@@ -90,7 +90,16 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "lz4_block.jsonl"))
     ap.add_argument("--sizes-only", action="store_true")
+    ap.add_argument("--search", type=lambda v: int(v, 0), nargs="+",
+                    help="search words (depth 1, 2, 4 or 8, plus 0x100 for LAZY; 0: the one-candidate search): "
+                         "only their encode rows are taken, and appended to the file")
     args = ap.parse_args()
+    if args.search:
+        with open(args.out, "a") as f:
+            for r in search_rows(args.iters, args.search):
+                f.write(json.dumps(r) + "\n")
+                print(json.dumps(r), flush=True)
+        return
     L = liblz4()
     rows = size_rows(L)
     if not args.sizes_only:
@@ -99,6 +108,41 @@ def main():
         for r in rows:
             f.write(json.dumps(r) + "\n")
             print(json.dumps(r))
+
+
+def search_rows(iters, words):
+    """One "encode_search" row per shape of gpu_rows and search word: the whole call, timed as there."""
+    import torch
+
+    assert torch.cuda.is_available(), "lz4_bench --search needs a GPU"
+    rows = []
+    for kind in ("sentence", "low_entropy"):
+        host = np.frombuffer(generate(kind, 16 << 20, 7), np.uint8)
+        for nblocks, mib in ((256, 1), (16, 16)):
+            bs = mib << 20
+            total = nblocks * bs
+            d_in = torch.from_numpy(np.concatenate([np.roll(host, 4099 * b)[:bs] for b in range(nblocks)])).to("cuda")
+            offs, sizes = [b * bs for b in range(nblocks)], [bs] * nblocks
+            for w in words:
+                res = Z.encode_batch(d_in, offs, sizes, search=w)
+                torch.cuda.synchronize()
+                res.check()
+                comp = int(res.sizes.sum().item())
+                for _ in range(2):
+                    Z.encode_batch(d_in, offs, sizes, search=w)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(iters):
+                    Z.encode_batch(d_in, offs, sizes, search=w)
+                b.record()
+                torch.cuda.synchronize()
+                t = a.elapsed_time(b) / 1e3 / iters
+                rows.append({"what": "encode_search", "device": torch.cuda.get_device_name(0), "data": kind,
+                             "blocks": nblocks, "block_bytes": bs, "iters": iters, "search": w, "seconds": t,
+                             "gib_per_s": total / GIB / t, "compressed_bytes": comp, "ratio": comp / total})
+            del d_in
+    return rows
 
 
 def gpu_rows(iters, L):

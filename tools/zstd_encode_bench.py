@@ -12,6 +12,10 @@ no kernels).  "lz4_seconds" is rpp_lz4_encode_batch on the same inputs, in the s
 rows are first measurements, the baseline a tuning change starts from.  `--options` lists the encoder's options
 words (rpp_zstd_encode_batch_opt: 1 per-block table modes, 2 repeat offsets, 3 both); every batch is encoded with
 each of them, one row per batch and options word ("options"), and the rows are appended to the file.
+`--search WORD...` lists search words (rpp_zstd_encode_batch_search and rpp_lz4_encode_batch_search: depth 1, 2, 4
+or 8, plus 0x100 for LAZY; 0, the default, is the one-candidate search): one row per batch, options word and search
+word ("search"), with the LZ4 figures of the same word; "kernels_seconds" then lists the deep search kernel under
+"rpp_lz4_search_kernel".
 """
 import argparse
 import ctypes as C
@@ -42,6 +46,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--options", type=int, nargs="+", default=[0])
+    ap.add_argument("--search", type=lambda v: int(v, 0), nargs="+", default=[0])
     ap.add_argument("--out", default=str(ROOT / "profiles" / "zstd_encode.jsonl"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "zstd_encode_bench needs a GPU"
@@ -63,10 +68,12 @@ def main():
         d_in, in_offs = _upload(blocks, dev)
         arrays = [S._i64(in_offs, dev), S._i64(sizes, dev)]
         results = {}
-        codecs = [(("zstd", o), Z.bound, N.lib().rpp_zstd_encode_workspace_bytes,
-                   lambda *a, o=o: N.lib().rpp_zstd_encode_batch_opt(*a[:4], o, *a[4:])) for o in args.options]
-        codecs.append((("lz4", 0), lz4.bound, N.lib().rpp_lz4_encode_workspace_bytes, N.lib().rpp_lz4_encode_batch))
-        for (codec, options), bound, ws_of, call_of in codecs:
+        codecs = [(("zstd", o, w), Z.bound, N.lib().rpp_zstd_encode_workspace_bytes,
+                   lambda *a, o=o, w=w: N.lib().rpp_zstd_encode_batch_search(*a[:4], o, w, *a[4:]))
+                  for o in args.options for w in args.search]
+        codecs += [(("lz4", 0, w), lz4.bound, N.lib().rpp_lz4_encode_workspace_bytes,
+                    lambda *a, w=w: N.lib().rpp_lz4_encode_batch_search(*a[:4], w, *a[4:])) for w in args.search]
+        for (codec, options, search), bound, ws_of, call_of in codecs:
             out_offs, cap = _layout([bound(s) for s in sizes])
             out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
             d_ooff = S._i64(out_offs, dev)
@@ -107,7 +114,7 @@ def main():
                     found = {}
                     for e in prof.key_averages():
                         for k in KERNELS:
-                            if k in e.key:
+                            if k in e.key.replace("rpp_lz4_deep_search_kernel", "rpp_lz4_search_kernel"):
                                 us = getattr(e, "device_time_total", None)
                                 if us is None:
                                     us = e.cuda_time_total
@@ -115,12 +122,13 @@ def main():
                     kernels = found if len(found) == len(KERNELS) else None
                 except Exception as e:  # the trace is an extra: the row stands without it
                     print(f"no kernel trace: {e}", file=sys.stderr)
-            results[codec, options] = (a.elapsed_time(b) / 1e3 / args.iters, int(out_sizes.sum().item()), ws_bytes, kernels)
+            results[codec, options, search] = (a.elapsed_time(b) / 1e3 / args.iters, int(out_sizes.sum().item()), ws_bytes, kernels)
             del out, ws
-        t_lz4, lz4_bytes, _, _ = results["lz4", 0]
-        for o in args.options:
-            t, frame_bytes, ws_bytes, kernels = results["zstd", o]
+        for o, w in ((o, w) for o in args.options for w in args.search):
+            t_lz4, lz4_bytes, _, _ = results["lz4", 0, w]
+            t, frame_bytes, ws_bytes, kernels = results["zstd", o, w]
             rows.append({"what": "encode", "device": torch.cuda.get_device_name(0), "shape": shape, "options": o,
+                         "search": w,
                          "blocks": n, "input_bytes": total, "frame_bytes": frame_bytes, "lz4_bytes": lz4_bytes,
                          "workspace_bytes": ws_bytes, "iters": args.iters, "seconds": t, "gib_per_s": total / GIB / t,
                          "kernels_seconds": kernels, "lz4_seconds": t_lz4, "lz4_gib_per_s": total / GIB / t_lz4,
