@@ -154,6 +154,9 @@ EXPORTED_SYMBOLS = (
     "rpp_lz4_host_encode_search",
     "rpp_zstd_encode_batch_search",
     "rpp_zstd_host_encode_search",
+    "rpp_incompressible_workspace_bytes",
+    "rpp_incompressible_scan_batch",
+    "rpp_incompressible_host_scan",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -522,6 +525,13 @@ def lib() -> C.CDLL:
         L.rpp_zstd_encode_batch_search.restype = C.c_int
         L.rpp_zstd_host_encode_search.argtypes = [P, U64, U32, U32, P, U64, C.POINTER(U64), C.POINTER(U32)]
         L.rpp_zstd_host_encode_search.restype = C.c_int
+        L.rpp_incompressible_workspace_bytes.argtypes = [U64, U32, U32]
+        L.rpp_incompressible_workspace_bytes.restype = U64
+        L.rpp_incompressible_scan_batch.argtypes = [P, P, P, U32, P, U32, C.c_double, U32, U32, U32, P, P, P, P, P, P,
+                                                    U64, P, U64, P]
+        L.rpp_incompressible_scan_batch.restype = C.c_int
+        L.rpp_incompressible_host_scan.argtypes = [P, P, P, U32, P, U32, C.c_double, U32, U32, U32, P, P, P, P, P, P]
+        L.rpp_incompressible_host_scan.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

@@ -45,6 +45,7 @@
 #include "lz4_internal.h"
 #include "ricepp_amd.h"
 #include "zstd_enc_common.h"
+#include "zstd_enc_internal.h"
 
 namespace {
 
@@ -542,7 +543,52 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_emit_kernel(const uint8_t*
 
 uint64_t align16(uint64_t v) { return (v + 15) & ~UINT64_C(15); }
 
+struct Stage {
+  EncodeWs ws;
+  ZstdWs zws;
+};
+
+// the workspace carved, then prep, search and entropy on the stream
+Stage launch_stage(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes, uint32_t nblocks,
+                   uint32_t options, uint32_t search, uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status,
+                   uint64_t total_bytes, void* d_workspace, void* stream) {
+  const uint64_t mc = rpp_lz4::max_chunks_of(total_bytes, nblocks);
+  const EncodeWs ws = rpp_lz4::carve_workspace(d_workspace, total_bytes, nblocks);
+  uint8_t* p = static_cast<uint8_t*>(d_workspace) + align16(rpp_lz4_encode_workspace_bytes(total_bytes, nblocks));
+  ZstdWs zws{};
+  zws.lits = p;
+  p += mc * kEncChunk;
+  zws.body = p;
+  p += mc * kEncChunk;
+  zws.tr = reinterpret_cast<uint32_t*>(p);
+  p += mc * kSeqsPerChunk * sizeof(uint32_t);
+  zws.kind = reinterpret_cast<uint32_t*>(p);
+  p += align16(4 * mc);
+  zws.size = reinterpret_cast<uint32_t*>(p);
+  p += align16(4 * mc);
+  zws.at = reinterpret_cast<uint32_t*>(p);
+  rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (options)
+    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<true>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
+                       d_in_bytes, nblocks, ws, zws, options);
+  else
+    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<false>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
+                       d_in_bytes, nblocks, ws, zws, options);
+  return Stage{ws, zws};
+}
+
 }  // namespace
+
+rpp_zstd::EntropyStage rpp_zstd::launch_search_entropy(const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                                       const uint64_t* d_in_bytes, uint32_t nblocks, uint32_t options,
+                                                       uint32_t search, uint64_t* d_out_bytes, uint32_t* d_flags,
+                                                       int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                                       void* stream) {
+  const Stage st = launch_stage(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, d_out_bytes, d_flags, d_status,
+                                total_bytes, d_workspace, stream);
+  return EntropyStage{st.ws, st.zws.size};
+}
 
 extern "C" uint64_t rpp_zstd_encode_workspace_bytes(uint64_t total_bytes, uint32_t nblocks) {
   const uint64_t mc = rpp_lz4::max_chunks_of(total_bytes, nblocks);
@@ -583,28 +629,11 @@ extern "C" int rpp_zstd_encode_batch_search(const uint8_t* d_in, const uint64_t*
   const uint64_t mc = rpp_lz4::max_chunks_of(total_bytes, nblocks);
   if (mc >= 0x7fffffffu) return RPP_INVALID_ARGUMENT;
   if (workspace_bytes < rpp_zstd_encode_workspace_bytes(total_bytes, nblocks)) return RPP_OUTPUT_TOO_SMALL;
-  const EncodeWs ws = rpp_lz4::carve_workspace(d_workspace, total_bytes, nblocks);
-  uint8_t* p = static_cast<uint8_t*>(d_workspace) + align16(rpp_lz4_encode_workspace_bytes(total_bytes, nblocks));
-  ZstdWs zws{};
-  zws.lits = p;
-  p += mc * kEncChunk;
-  zws.body = p;
-  p += mc * kEncChunk;
-  zws.tr = reinterpret_cast<uint32_t*>(p);
-  p += mc * kSeqsPerChunk * sizeof(uint32_t);
-  zws.kind = reinterpret_cast<uint32_t*>(p);
-  p += align16(4 * mc);
-  zws.size = reinterpret_cast<uint32_t*>(p);
-  p += align16(4 * mc);
-  zws.at = reinterpret_cast<uint32_t*>(p);
-  rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
+  const Stage st = launch_stage(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, d_out_bytes, d_flags, d_status,
+                                total_bytes, d_workspace, stream);
+  const EncodeWs& ws = st.ws;
+  const ZstdWs& zws = st.zws;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (options)
-    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<true>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
-                       d_in_bytes, nblocks, ws, zws, options);
-  else
-    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<false>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
-                       d_in_bytes, nblocks, ws, zws, options);
   hipLaunchKernelGGL(rpp_zstd_enc_place_kernel, dim3(nblocks), dim3(kWave), 0, s, d_in_bytes, ws, zws, d_out,
                      d_out_offsets, d_out_bytes, d_flags, d_status);
   hipLaunchKernelGGL(rpp_zstd_enc_emit_kernel, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets, nblocks, ws, zws,

@@ -1155,6 +1155,44 @@ int rpp_zstd_encode_batch_search(const uint8_t* d_in, const uint64_t* d_in_offse
 int rpp_zstd_host_encode_search(const uint8_t* in, uint64_t n, uint32_t options, uint32_t search, uint8_t* out,
                                 uint64_t capacity, uint64_t* out_bytes, uint32_t* bad_ratio);
 
+/*
+ * The incompressible categorizer of the scan (src/writer/categorizer/incompressible_categorizer.cpp): which
+ * pieces of a file are not worth a compressor.  An extent (a contiguous run of file data) is cut by the caller
+ * into pieces of block_size bytes (the last one may be shorter); piece p is d_in + d_in_offsets[p], d_in_bytes[p]
+ * bytes (at most RPP_LZ4_MAX_BLOCK), and extent e holds the pieces d_piece_base[e] .. d_piece_base[e + 1]
+ * (nextents + 1 entries that do not decrease and end at or below npieces; equal entries: an empty extent).
+ *   d_sizes[p]     the size of the one frame that rpp_zstd_encode_batch_search(options, search) writes for the
+ *                  piece, header included.  This encoder's size, not libzstd's; no frame is written.
+ *   d_verdicts[p]  1 (incompressible) iff double(size) >= max_ratio * double(n), else 0
+ *   d_totals       per extent RPP_INCOMPRESSIBLE_TOTALS numbers: total_in, total_out, blocks,
+ *                  incompressible_blocks, and the single-fragment verdict (blocks > 0 and
+ *                  double(total_out) >= max_ratio * double(total_in))
+ *   d_frag_rows    rows of (category, bytes), two uint64 each; npieces rows.  With generate_fragments, extent e's
+ *                  run-length list over its pieces (neighbours of one verdict merged; category 0 the default,
+ *                  1 incompressible) stands in the rows d_piece_base[e] .. + d_frag_count[e]; the rows behind
+ *                  them are not written.  Without it d_frag_count[e] is 0 and no row is written.
+ *   d_status[p]    RPP_OK, or RPP_INVALID_ARGUMENT for a piece that is too large or when the pieces hold more
+ *                  than total_bytes (then every piece); such a piece has size 0 and verdict 0.
+ * An unknown options bit or search word is RPP_INVALID_ARGUMENT; npieces == 0 is RPP_OK and writes nothing; a
+ * 16-aligned workspace below rpp_incompressible_workspace_bytes(total_bytes, npieces, nextents) bytes is
+ * RPP_OUTPUT_TOO_SMALL.  Asynchronous on the stream.  rpp_incompressible_host_scan computes the same numbers on the
+ * host (it refuses a d_piece_base that decreases or passes npieces; the kernels clamp).  The complete definition
+ * is at the top of dwarfs_amd/csrc/scan/incompressible_host.cpp.
+ */
+#define RPP_INCOMPRESSIBLE_TOTALS 5
+uint64_t rpp_incompressible_workspace_bytes(uint64_t total_bytes, uint32_t npieces, uint32_t nextents);
+int rpp_incompressible_scan_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                                  uint32_t npieces, const uint32_t* d_piece_base, uint32_t nextents, double max_ratio,
+                                  uint32_t generate_fragments, uint32_t options, uint32_t search, uint64_t* d_sizes,
+                                  uint32_t* d_verdicts, uint64_t* d_totals, uint64_t* d_frag_rows,
+                                  uint32_t* d_frag_count, int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                  uint64_t workspace_bytes, void* stream);
+int rpp_incompressible_host_scan(const uint8_t* in, const uint64_t* in_offsets, const uint64_t* in_bytes,
+                                 uint32_t npieces, const uint32_t* piece_base, uint32_t nextents, double max_ratio,
+                                 uint32_t generate_fragments, uint32_t options, uint32_t search, uint64_t* sizes,
+                                 uint32_t* verdicts, uint64_t* totals, uint64_t* frag_rows, uint32_t* frag_count,
+                                 int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
