@@ -157,6 +157,13 @@ EXPORTED_SYMBOLS = (
     "rpp_incompressible_workspace_bytes",
     "rpp_incompressible_scan_batch",
     "rpp_incompressible_host_scan",
+    "rpp_zstd_encode_workspace_bytes_long",
+    "rpp_zstd_encode_batch_long",
+    "rpp_zstd_host_encode_long",
+    "rpp_zstd_host_long_sequences",
+    "rpp_incompressible_workspace_bytes_long",
+    "rpp_incompressible_scan_batch_long",
+    "rpp_incompressible_host_scan_long",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -166,6 +173,7 @@ RPP_HASH_SHA512_256 = 2
 RPP_ZSTD_ENC_TABLES = 1  # the options word of rpp_zstd_encode_batch_opt / rpp_zstd_host_encode_opt
 RPP_ZSTD_ENC_REPEAT = 2
 RPP_SEARCH_LAZY = 0x100  # the search word of the *_search calls: depth (1, 2, 4, 8) | RPP_SEARCH_LAZY
+RPP_ZSTD_LONG_MAX_BLOCK = 1 << 27  # a block's largest size under the `long` word of the *_long calls
 
 RPP_SIMILARITY_NILSIMSA = 0
 RPP_SIMILARITY_HISTOGRAM = 1
@@ -532,6 +540,22 @@ def lib() -> C.CDLL:
         L.rpp_incompressible_scan_batch.restype = C.c_int
         L.rpp_incompressible_host_scan.argtypes = [P, P, P, U32, P, U32, C.c_double, U32, U32, U32, P, P, P, P, P, P]
         L.rpp_incompressible_host_scan.restype = C.c_int
+        L.rpp_zstd_encode_workspace_bytes_long.argtypes = [U64, U32, U32]
+        L.rpp_zstd_encode_workspace_bytes_long.restype = U64
+        L.rpp_zstd_encode_batch_long.argtypes = [P, P, P, U32, U32, U32, U32, P, P, P, P, P, U64, P, U64, P]
+        L.rpp_zstd_encode_batch_long.restype = C.c_int
+        L.rpp_zstd_host_encode_long.argtypes = [P, U64, U32, U32, U32, P, U64, C.POINTER(U64), C.POINTER(U32)]
+        L.rpp_zstd_host_encode_long.restype = C.c_int
+        L.rpp_zstd_host_long_sequences.argtypes = [P, U64, U32, U32, P, U64, C.POINTER(U64)]
+        L.rpp_zstd_host_long_sequences.restype = C.c_int
+        L.rpp_incompressible_workspace_bytes_long.argtypes = [U64, U32, U32, U32]
+        L.rpp_incompressible_workspace_bytes_long.restype = U64
+        L.rpp_incompressible_scan_batch_long.argtypes = [P, P, P, U32, P, U32, C.c_double, U32, U32, U32, U32, P, P, P,
+                                                         P, P, P, U64, P, U64, P]
+        L.rpp_incompressible_scan_batch_long.restype = C.c_int
+        L.rpp_incompressible_host_scan_long.argtypes = [P, P, P, U32, P, U32, C.c_double, U32, U32, U32, U32, P, P, P, P,
+                                                        P, P]
+        L.rpp_incompressible_host_scan_long.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

@@ -31,7 +31,7 @@ import torch
 from . import _native as N
 from .codec import _raise_status, _stream_ptr
 from .lz4 import MAX_BLOCK, _ptr, check_search
-from .zstd import ENC_ADAPTIVE
+from .zstd import ENC_ADAPTIVE, LONG_MAX_BLOCK, check_long
 
 DEFAULT_CATEGORY = "<default>"  # categorizer::DEFAULT_CATEGORY
 INCOMPRESSIBLE_CATEGORY = "incompressible"
@@ -66,6 +66,7 @@ class IncompressibleConfig:
     max_ratio: float = 0.99
     options: int = 0
     search: int = 0
+    long: int = 0  # the encoder's long word (zstd.py): 1 lets a piece match anything earlier in itself
 
     def __post_init__(self):
         object.__setattr__(self, "min_input_size", parse_size_with_unit(self.min_input_size))
@@ -78,6 +79,9 @@ class IncompressibleConfig:
             raise ValueError(f"unknown zstd encoder options: {self.options}")
         object.__setattr__(self, "options", int(self.options))
         object.__setattr__(self, "search", check_search(self.search))
+        object.__setattr__(self, "long", check_long(self.long))
+        if self.long and self.block_size > LONG_MAX_BLOCK:
+            raise ValueError(f"block_size must be at most {LONG_MAX_BLOCK} with long=1, not {self.block_size}")
 
 
 class Hole(NamedTuple):
@@ -152,12 +156,12 @@ def scan_batch(d_in: torch.Tensor, in_offsets, in_sizes, piece_base, cfg: Incomp
                torch.zeros((npieces, 2), dtype=torch.int64, device=dev),
                torch.zeros(nextents, dtype=torch.int32, device=dev), torch.zeros(npieces, dtype=torch.int32, device=dev))
     sizes, verdicts, totals, rows, count, status = out
-    ws_bytes = int(N.lib().rpp_incompressible_workspace_bytes(total, npieces, nextents))
+    ws_bytes = int(N.lib().rpp_incompressible_workspace_bytes_long(total, npieces, nextents, cfg.long))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    _raise_status(N.lib().rpp_incompressible_scan_batch(
+    _raise_status(N.lib().rpp_incompressible_scan_batch_long(
         _ptr(d_in), _ptr(d_off), _ptr(d_sz), npieces, _ptr(d_base), nextents, cfg.max_ratio,
-        int(cfg.generate_fragments), cfg.options, cfg.search, _ptr(sizes), _ptr(verdicts), _ptr(totals), _ptr(rows),
-        _ptr(count), _ptr(status), total, _ptr(ws), ws_bytes, _stream_ptr(stream)))
+        int(cfg.generate_fragments), cfg.options, cfg.search, cfg.long, _ptr(sizes), _ptr(verdicts), _ptr(totals),
+        _ptr(rows), _ptr(count), _ptr(status), total, _ptr(ws), ws_bytes, _stream_ptr(stream)))
     return out
 
 
@@ -170,9 +174,9 @@ def host_scan(flat: np.ndarray, in_offsets, in_sizes, piece_base, cfg: Incompres
         out = (np.zeros(npieces, np.uint64), np.zeros(npieces, np.uint32), np.zeros((nextents, TOTALS), np.uint64),
                np.zeros((npieces, 2), np.uint64), np.zeros(nextents, np.uint32), np.zeros(npieces, np.int32))
     p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-    _raise_status(N.lib().rpp_incompressible_host_scan(
+    _raise_status(N.lib().rpp_incompressible_host_scan_long(
         p(flat), p(offs), p(szs), npieces, p(base), nextents, cfg.max_ratio, int(cfg.generate_fragments), cfg.options,
-        cfg.search, *(p(a) for a in out)))
+        cfg.search, cfg.long, *(p(a) for a in out)))
     return out
 
 

@@ -161,6 +161,12 @@ extern "C" uint64_t rpp_incompressible_workspace_bytes(uint64_t total_bytes, uin
   return align16(rpp_zstd_encode_workspace_bytes(total_bytes, npieces));
 }
 
+extern "C" uint64_t rpp_incompressible_workspace_bytes_long(uint64_t total_bytes, uint32_t npieces,
+                                                            uint32_t nextents, uint32_t long_mode) {
+  (void)nextents;
+  return align16(rpp_zstd_encode_workspace_bytes_long(total_bytes, npieces, long_mode));
+}
+
 extern "C" int rpp_incompressible_scan_batch(const uint8_t* d_in, const uint64_t* d_in_offsets,
                                              const uint64_t* d_in_bytes, uint32_t npieces,
                                              const uint32_t* d_piece_base, uint32_t nextents, double max_ratio,
@@ -169,16 +175,33 @@ extern "C" int rpp_incompressible_scan_batch(const uint8_t* d_in, const uint64_t
                                              uint64_t* d_frag_rows, uint32_t* d_frag_count, int32_t* d_status,
                                              uint64_t total_bytes, void* d_workspace, uint64_t workspace_bytes,
                                              void* stream) {
-  if ((options & ~rpp_zstd::kEncOptionsMask) || !rpp_lz4::search_valid(search)) return RPP_INVALID_ARGUMENT;
+  return rpp_incompressible_scan_batch_long(d_in, d_in_offsets, d_in_bytes, npieces, d_piece_base, nextents, max_ratio,
+                                            generate_fragments, options, search, 0, d_sizes, d_verdicts, d_totals,
+                                            d_frag_rows, d_frag_count, d_status, total_bytes, d_workspace,
+                                            workspace_bytes, stream);
+}
+
+// ... under the Zstandard encoder's `long` word (0: the call above); the sizes are rpp_zstd_encode_batch_long's
+extern "C" int rpp_incompressible_scan_batch_long(const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                                  const uint64_t* d_in_bytes, uint32_t npieces,
+                                                  const uint32_t* d_piece_base, uint32_t nextents, double max_ratio,
+                                                  uint32_t generate_fragments, uint32_t options, uint32_t search,
+                                                  uint32_t long_mode, uint64_t* d_sizes, uint32_t* d_verdicts,
+                                                  uint64_t* d_totals, uint64_t* d_frag_rows, uint32_t* d_frag_count,
+                                                  int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                                  uint64_t workspace_bytes, void* stream) {
+  if ((options & ~rpp_zstd::kEncOptionsMask) || !rpp_lz4::search_valid(search) || long_mode > 1)
+    return RPP_INVALID_ARGUMENT;
   if (npieces == 0) return RPP_OK;
   if (!d_in || !d_in_offsets || !d_in_bytes || !d_sizes || !d_verdicts || !d_frag_rows || !d_status || !d_workspace ||
       ((uintptr_t)d_workspace & 15) || (nextents && (!d_piece_base || !d_totals || !d_frag_count)))
     return RPP_INVALID_ARGUMENT;
   if (rpp_lz4::max_chunks_of(total_bytes, npieces) >= 0x7fffffffu) return RPP_INVALID_ARGUMENT;
-  if (workspace_bytes < rpp_incompressible_workspace_bytes(total_bytes, npieces, nextents)) return RPP_OUTPUT_TOO_SMALL;
+  if (workspace_bytes < rpp_incompressible_workspace_bytes_long(total_bytes, npieces, nextents, long_mode))
+    return RPP_OUTPUT_TOO_SMALL;
   const rpp_zstd::EntropyStage st =
-      rpp_zstd::launch_search_entropy(d_in, d_in_offsets, d_in_bytes, npieces, options, search, d_sizes, d_verdicts,
-                                      d_status, total_bytes, d_workspace, stream);
+      rpp_zstd::launch_search_entropy(d_in, d_in_offsets, d_in_bytes, npieces, options, search, long_mode, d_sizes,
+                                      d_verdicts, d_status, total_bytes, d_workspace, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(rpp_incompressible_classify_kernel, dim3(npieces), dim3(kWave), 0, s, d_in_bytes, npieces, st.ws,
                      st.block_size, d_status, max_ratio, d_sizes, d_verdicts);

@@ -46,6 +46,8 @@
 #include "ricepp_amd.h"
 #include "zstd_enc_common.h"
 #include "zstd_enc_internal.h"
+#include "zstd_long_common.h"
+#include "zstd_long_internal.h"
 
 namespace {
 
@@ -60,6 +62,23 @@ constexpr uint32_t kTileBits = 4096;  // what one turn adds, at most: 256 codes 
 constexpr uint32_t kLitsPerLane = 4;  // (with own tables 63: three moves of kOwnLogMax bits, 15 extra bits thrice)
 static_assert(kWave * kLitsPerLane * kHufLog <= kTileBits && kWave * (3 * kOwnLogMax + 45) <= kTileBits,
               "a turn fits the window");
+// With the `long` word an offset's extra bits reach 27 where they stayed at 15: a turn of 64 sequences adds more.
+constexpr uint32_t kTileBitsLong = kWave * (3 * kOwnLogMax + 30 + 27);
+static_assert(kTileBitsLong + 32 <= 32 * kWinWords / 2, "a turn of wide offsets fits the window");
+
+// The fields of a workspace record.  kLong: the widened record (zstd_long_common.h), whose offset continues in
+// the upper half of .y; without it the short search's record as it always was.
+template <bool kLong>
+__device__ inline uint32_t seq_len(uint2 s) {
+  if constexpr (kLong) return rpp_zstd_long::rec_len(s.y);
+  else return s.y;
+}
+
+template <bool kLong>
+__device__ inline uint32_t seq_off(uint2 s) {
+  if constexpr (kLong) return rpp_zstd_long::rec_off(s.x, s.y);
+  else return s.x >> 16;
+}
 
 struct ZstdWs {
   uint8_t* lits;   // per chunk: [kEncChunk] its literals
@@ -125,9 +144,10 @@ __device__ inline void win_put(const Win& win, uint32_t pos, uint32_t v, uint32_
   if (sh + nb > 32) atomicOr(&win.w[word + 1], v >> (32 - sh));
 }
 
-// room for a turn of kTileBits bits from `pos` on (uniform): stores the full words when the window runs short
+// room for a turn of kTurnBits bits from `pos` on (uniform): stores the full words when the window runs short
+template <uint32_t kTurnBits = kTileBits>
 __device__ inline void win_room(Win& win, uint32_t pos, uint32_t lane) {
-  if (pos - 32 * win.flushed + kTileBits + 32 <= 32 * kWinWords) return;
+  if (pos - 32 * win.flushed + kTurnBits + 32 <= 32 * kWinWords) return;
   __syncthreads();
   const uint32_t full = (pos >> 5) - win.flushed;
   for (uint32_t k = lane; k < full; k += kWave) {
@@ -189,20 +209,22 @@ struct SeqView {  // sequence i of a chunk that starts at cs
   uint32_t ll, ml, ov;
 };
 
+template <bool kLong>
 __device__ inline SeqView seq_view(const uint2* seqs, uint32_t i, uint32_t cs) {
   const uint2 s = seqs[i];
   uint32_t prev = cs;
   if (i) {
     const uint2 p = seqs[i - 1];
-    prev = cs + (p.x & 0xffffu) + p.y;
+    prev = cs + (p.x & 0xffffu) + seq_len<kLong>(p);
   }
-  return SeqView{cs + (s.x & 0xffffu) - prev, s.y, (s.x >> 16) + 3};
+  return SeqView{cs + (s.x & 0xffffu) - prev, seq_len<kLong>(s), seq_off<kLong>(s) + 3};
 }
 
 // ... with the offset value of the repeat-offset rule
+template <bool kLong>
 __device__ inline SeqView seq_view_repeat(const uint2* seqs, uint32_t i, uint32_t cs) {
-  SeqView v = seq_view(seqs, i, cs);
-  const uint32_t off1 = i >= 1 ? seqs[i - 1].x >> 16 : 0, off2 = i >= 2 ? seqs[i - 2].x >> 16 : 0;
+  SeqView v = seq_view<kLong>(seqs, i, cs);
+  const uint32_t off1 = i >= 1 ? seq_off<kLong>(seqs[i - 1]) : 0, off2 = i >= 2 ? seq_off<kLong>(seqs[i - 2]) : 0;
   v.ov = offset_value(v.ov - 3, off1, off2, v.ll, i);
   return v;
 }
@@ -210,7 +232,7 @@ __device__ inline SeqView seq_view_repeat(const uint2* seqs, uint32_t i, uint32_
 // ---------------------------------------------------------------------------
 // entropy: one wave per chunk
 // ---------------------------------------------------------------------------
-template <bool kOpt>  // kOpt: options != 0
+template <bool kOpt, bool kLong>  // kOpt: options != 0; kLong: the sequences are widened records (long = 1)
 __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8_t* __restrict__ d_in,
                                                                 const uint64_t* __restrict__ in_offsets,
                                                                 const uint64_t* __restrict__ n_bytes,
@@ -250,15 +272,15 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
     const uint32_t i = t + lane, here = min(cnt - t, kWave);
     const bool has = i < cnt;
     const uint2 s = has ? seqs[i] : make_uint2(0, 0);
-    const uint32_t pos = cs + (s.x & 0xffffu), len = s.y;
+    const uint32_t pos = cs + (s.x & 0xffffu), len = seq_len<kLong>(s);
     const uint32_t end = has ? pos + len : 0;
     uint32_t prev = __shfl_up(end, 1);
     if (lane == 0) prev = prev_end;
     const uint32_t lit = has ? pos - prev : 0;
     const uint32_t incl = wave_incl_sum(lit, lane), mine = m + incl - lit;
-    uint32_t ov = (s.x >> 16) + 3;
+    uint32_t ov = seq_off<kLong>(s) + 3;
     if constexpr (kOpt) {
-      const uint32_t off = s.x >> 16;
+      const uint32_t off = seq_off<kLong>(s);
       uint32_t off1 = __shfl_up(off, 1), off2 = __shfl_up(off, 2);
       if (lane == 0) off1 = off_carry1;
       if (lane < 2) off2 = lane == 0 ? off_carry2 : off_carry1;
@@ -440,15 +462,16 @@ __global__ __launch_bounds__(kWave) void rpp_zstd_enc_entropy_kernel(const uint8
   win_open(win, win_words, q + head, lane);
   uint32_t pos = 0;
   for (uint32_t t = 0; t < cnt; t += kWave) {
-    win_room(win, pos, lane);
+    win_room<kLong ? kTileBitsLong : kTileBits>(win, pos, lane);
     const uint32_t r = t + lane;  // counted from the end
     const bool has = r < cnt;
     SeqCodes c{};
     uint32_t f[3] = {0, 0, 0}, width = 0;
     if (has) {
       SeqView v;
-      if constexpr (kOpt) v = options & kEncRepeat ? seq_view_repeat(seqs, cnt - 1 - r, cs) : seq_view(seqs, cnt - 1 - r, cs);
-      else v = seq_view(seqs, cnt - 1 - r, cs);
+      if constexpr (kOpt)
+        v = options & kEncRepeat ? seq_view_repeat<kLong>(seqs, cnt - 1 - r, cs) : seq_view<kLong>(seqs, cnt - 1 - r, cs);
+      else v = seq_view<kLong>(seqs, cnt - 1 - r, cs);
       c = sequence_codes(v.ll, v.ml, v.ov);
       const uint32_t moved = tr[cnt - 1 - r];
       for (uint32_t k = 0; k < 3; ++k) f[k] = moved >> (9 * k) & 511;
@@ -546,14 +569,30 @@ uint64_t align16(uint64_t v) { return (v + 15) & ~UINT64_C(15); }
 struct Stage {
   EncodeWs ws;
   ZstdWs zws;
+  const uint64_t* n_bytes;  // the blocks' sizes as the kernels take them
 };
 
-// the workspace carved, then prep, search and entropy on the stream
+template <bool kLong>
+void launch_entropy(hipStream_t s, uint32_t mc, const uint8_t* d_in, const uint64_t* d_in_offsets,
+                    const uint64_t* d_in_bytes, uint32_t nblocks, const EncodeWs& ws, const ZstdWs& zws,
+                    uint32_t options) {
+  if (options)
+    hipLaunchKernelGGL((rpp_zstd_enc_entropy_kernel<true, kLong>), dim3(mc), dim3(kWave), 0, s, d_in, d_in_offsets,
+                       d_in_bytes, nblocks, ws, zws, options);
+  else
+    hipLaunchKernelGGL((rpp_zstd_enc_entropy_kernel<false, kLong>), dim3(mc), dim3(kWave), 0, s, d_in, d_in_offsets,
+                       d_in_bytes, nblocks, ws, zws, options);
+}
+
+// The workspace carved, then prep, search and entropy on the stream.  With long_mode the long-distance matcher's
+// launches (zstd_long.hip) stand around the search: the entropy kernel and everything behind it then read the
+// merged lists in the short lists' place and the sizes in st.n_bytes, where an over-size block is one that the
+// prep kernel has refused.
 Stage launch_stage(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes, uint32_t nblocks,
-                   uint32_t options, uint32_t search, uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status,
-                   uint64_t total_bytes, void* d_workspace, void* stream) {
+                   uint32_t options, uint32_t search, uint32_t long_mode, uint64_t* d_out_bytes, uint32_t* d_flags,
+                   int32_t* d_status, uint64_t total_bytes, void* d_workspace, void* stream) {
   const uint64_t mc = rpp_lz4::max_chunks_of(total_bytes, nblocks);
-  const EncodeWs ws = rpp_lz4::carve_workspace(d_workspace, total_bytes, nblocks);
+  EncodeWs ws = rpp_lz4::carve_workspace(d_workspace, total_bytes, nblocks);
   uint8_t* p = static_cast<uint8_t*>(d_workspace) + align16(rpp_lz4_encode_workspace_bytes(total_bytes, nblocks));
   ZstdWs zws{};
   zws.lits = p;
@@ -567,26 +606,32 @@ Stage launch_stage(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint
   zws.size = reinterpret_cast<uint32_t*>(p);
   p += align16(4 * mc);
   zws.at = reinterpret_cast<uint32_t*>(p);
-  rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (options)
-    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<true>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
-                       d_in_bytes, nblocks, ws, zws, options);
-  else
-    hipLaunchKernelGGL(rpp_zstd_enc_entropy_kernel<false>, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets,
-                       d_in_bytes, nblocks, ws, zws, options);
-  return Stage{ws, zws};
+  if (!long_mode) {
+    rpp_lz4::launch_search(d_in, d_in_offsets, d_in_bytes, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
+    launch_entropy<false>(s, uint32_t(mc), d_in, d_in_offsets, d_in_bytes, nblocks, ws, zws, options);
+    return Stage{ws, zws, d_in_bytes};
+  }
+  p += align16(4 * mc);
+  const rpp_zstd_long::LongWs lws = rpp_zstd_long::carve(p, total_bytes, nblocks);
+  rpp_zstd_long::launch_prepare(d_in_bytes, nblocks, lws, stream);
+  rpp_lz4::launch_search(d_in, d_in_offsets, lws.n_eff, nblocks, ws, d_out_bytes, d_flags, d_status, search, stream);
+  rpp_zstd_long::launch_match(d_in, d_in_offsets, nblocks, ws, lws, stream);
+  ws.cnt = lws.mcnt;
+  ws.seqs = lws.mseqs;
+  launch_entropy<true>(s, uint32_t(mc), d_in, d_in_offsets, lws.n_eff, nblocks, ws, zws, options);
+  return Stage{ws, zws, lws.n_eff};
 }
 
 }  // namespace
 
 rpp_zstd::EntropyStage rpp_zstd::launch_search_entropy(const uint8_t* d_in, const uint64_t* d_in_offsets,
                                                        const uint64_t* d_in_bytes, uint32_t nblocks, uint32_t options,
-                                                       uint32_t search, uint64_t* d_out_bytes, uint32_t* d_flags,
-                                                       int32_t* d_status, uint64_t total_bytes, void* d_workspace,
-                                                       void* stream) {
-  const Stage st = launch_stage(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, d_out_bytes, d_flags, d_status,
-                                total_bytes, d_workspace, stream);
+                                                       uint32_t search, uint32_t long_mode, uint64_t* d_out_bytes,
+                                                       uint32_t* d_flags, int32_t* d_status, uint64_t total_bytes,
+                                                       void* d_workspace, void* stream) {
+  const Stage st = launch_stage(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, long_mode, d_out_bytes, d_flags,
+                                d_status, total_bytes, d_workspace, stream);
   return EntropyStage{st.ws, st.zws.size};
 }
 
@@ -594,6 +639,11 @@ extern "C" uint64_t rpp_zstd_encode_workspace_bytes(uint64_t total_bytes, uint32
   const uint64_t mc = rpp_lz4::max_chunks_of(total_bytes, nblocks);
   return align16(rpp_lz4_encode_workspace_bytes(total_bytes, nblocks)) + 2 * mc * kEncChunk +
          mc * kSeqsPerChunk * sizeof(uint32_t) + 3 * align16(4 * mc);
+}
+
+extern "C" uint64_t rpp_zstd_encode_workspace_bytes_long(uint64_t total_bytes, uint32_t nblocks, uint32_t long_mode) {
+  const uint64_t base = rpp_zstd_encode_workspace_bytes(total_bytes, nblocks);
+  return long_mode ? base + rpp_zstd_long::workspace_bytes(total_bytes, nblocks) : base;
 }
 
 extern "C" int rpp_zstd_encode_batch(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
@@ -621,20 +671,32 @@ extern "C" int rpp_zstd_encode_batch_search(const uint8_t* d_in, const uint64_t*
                                             uint64_t* d_out_bytes, uint32_t* d_flags, int32_t* d_status,
                                             uint64_t total_bytes, void* d_workspace, uint64_t workspace_bytes,
                                             void* stream) {
-  if ((options & ~kEncOptionsMask) || !rpp_lz4::search_valid(search)) return RPP_INVALID_ARGUMENT;
+  return rpp_zstd_encode_batch_long(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, 0, d_out, d_out_offsets,
+                                    d_out_bytes, d_flags, d_status, total_bytes, d_workspace, workspace_bytes, stream);
+}
+
+static_assert(RPP_ZSTD_LONG_MAX_BLOCK == rpp_zstd_long::kLongMaxBlock, "the long word's largest block");
+
+extern "C" int rpp_zstd_encode_batch_long(const uint8_t* d_in, const uint64_t* d_in_offsets,
+                                          const uint64_t* d_in_bytes, uint32_t nblocks, uint32_t options,
+                                          uint32_t search, uint32_t long_mode, uint8_t* d_out,
+                                          const uint64_t* d_out_offsets, uint64_t* d_out_bytes, uint32_t* d_flags,
+                                          int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                          uint64_t workspace_bytes, void* stream) {
+  if ((options & ~kEncOptionsMask) || !rpp_lz4::search_valid(search) || long_mode > 1) return RPP_INVALID_ARGUMENT;
   if (nblocks == 0) return RPP_OK;
   if (!d_in || !d_in_offsets || !d_in_bytes || !d_out || !d_out_offsets || !d_out_bytes || !d_flags || !d_status ||
       !d_workspace || ((uintptr_t)d_workspace & 15))
     return RPP_INVALID_ARGUMENT;
   const uint64_t mc = rpp_lz4::max_chunks_of(total_bytes, nblocks);
   if (mc >= 0x7fffffffu) return RPP_INVALID_ARGUMENT;
-  if (workspace_bytes < rpp_zstd_encode_workspace_bytes(total_bytes, nblocks)) return RPP_OUTPUT_TOO_SMALL;
-  const Stage st = launch_stage(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, d_out_bytes, d_flags, d_status,
-                                total_bytes, d_workspace, stream);
+  if (workspace_bytes < rpp_zstd_encode_workspace_bytes_long(total_bytes, nblocks, long_mode)) return RPP_OUTPUT_TOO_SMALL;
+  const Stage st = launch_stage(d_in, d_in_offsets, d_in_bytes, nblocks, options, search, long_mode, d_out_bytes, d_flags,
+                                d_status, total_bytes, d_workspace, stream);
   const EncodeWs& ws = st.ws;
   const ZstdWs& zws = st.zws;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(rpp_zstd_enc_place_kernel, dim3(nblocks), dim3(kWave), 0, s, d_in_bytes, ws, zws, d_out,
+  hipLaunchKernelGGL(rpp_zstd_enc_place_kernel, dim3(nblocks), dim3(kWave), 0, s, st.n_bytes, ws, zws, d_out,
                      d_out_offsets, d_out_bytes, d_flags, d_status);
   hipLaunchKernelGGL(rpp_zstd_enc_emit_kernel, dim3(uint32_t(mc)), dim3(kWave), 0, s, d_in, d_in_offsets, nblocks, ws, zws,
                      d_out, d_out_offsets);

@@ -110,6 +110,7 @@
 #include "lz4_internal.h"
 #include "ricepp_amd.h"
 #include "zstd_enc_common.h"
+#include "zstd_long_internal.h"
 
 namespace {
 
@@ -252,8 +253,13 @@ uint32_t write_sequences(const rpp_lz4::Seq* seqs, uint32_t count, uint32_t cs, 
     p += plan[k].desc_bytes;
   }
   uint32_t pos = 0;
-  auto put = [&](uint32_t v, uint32_t nb) {
-    put_bits(p, pos, v, nb);
+  auto put = [&](uint32_t v, uint32_t nb) {  // (put_bits takes 16 bits; an offset's extra bits reach 27 with long = 1)
+    if (nb > 16) {
+      put_bits(p, pos, v & 0xffffu, 16);
+      put_bits(p, pos + 16, v >> 16, nb - 16);
+    } else {
+      put_bits(p, pos, v, nb);
+    }
     pos += nb;
   };
   for (uint32_t i = count; i-- > 0;) {
@@ -296,9 +302,18 @@ extern "C" int rpp_zstd_host_encode_search(const uint8_t* in, uint64_t n, uint32
     return RPP_INVALID_ARGUMENT;
   if (n > rpp_lz4::kMaxBlock) return RPP_INVALID_ARGUMENT;
   if (capacity < encode_bound(n)) return RPP_OUTPUT_TOO_SMALL;
-  static const Tables tables;
   std::vector<rpp_lz4::Seq> seqs;
   rpp_lz4::find_sequences(in, uint32_t(n), seqs, search);
+  rpp_zstd::write_frame(in, uint32_t(n), options, seqs, out, out_bytes, bad_ratio);
+  return RPP_OK;
+}
+
+// The frame of a block of n bytes from its sequences (in order, none across a chunk's end), at out
+// (encode_bound(n) bytes): everything of the definition above behind the search.  Also the back end of
+// rpp_zstd_host_encode_long (zstd_long_host.cpp), whose sequences come from two searches.
+void rpp_zstd::write_frame(const uint8_t* in, uint32_t n, uint32_t options, const std::vector<rpp_lz4::Seq>& seqs,
+                           uint8_t* out, uint64_t* out_bytes, uint32_t* bad_ratio) {
+  static const Tables tables;
   uint8_t* o = out + frame_header(n, out);
   if (n == 0) {
     block_header(o, true, kRaw, 0);
@@ -340,5 +355,4 @@ extern "C" int rpp_zstd_host_encode_search(const uint8_t* in, uint64_t n, uint32
   }
   *out_bytes = uint64_t(o - out);
   if (bad_ratio) *bad_ratio = *out_bytes >= n ? 1u : 0u;  // bad_compression_ratio_error (zstd.cpp:435)
-  return RPP_OK;
 }

@@ -13,7 +13,10 @@ frame per block, one Zstandard block per 32 KiB chunk of the LZ4 encoder's match
 tables, no repeat offsets, no checksum; ``level`` is recorded and changes nothing (it maps to no search word).  The
 search word (``search=``, or ``depth=N`` and ``lazy=0|1`` in a spec; ``depth | SEARCH_LAZY``, see lz4.py) turns on the
 LZ4 encoder's deeper match search; 0, the default, is the one-candidate greedy search.  The options word
-(``ENC_TABLES``, ``ENC_REPEAT``; ``ENC_ADAPTIVE`` is both) turns on per-block table modes and repeat-offset codes.  ``compress`` raises
+(``ENC_TABLES``, ``ENC_REPEAT``; ``ENC_ADAPTIVE`` is both) turns on per-block table modes and repeat-offset codes.  The long
+word (``long=1``, or ``long`` / ``long=1`` in a spec given to ``block_compressor_long``, the reference's option at zstd.cpp:69 and :404-406) adds matches
+against anything earlier in the same block (defined at the top of csrc/zstd_long_host.cpp); a block then holds
+at most ``LONG_MAX_BLOCK`` bytes.  ``compress`` raises
 :class:`lz4.BadCompressionRatioError` when the frame is no smaller than the input; the writer then stores the
 block as type NONE, which ``compress_many_sections`` does.  ``zstd.block_compressor("zstd[:level=N]")`` makes
 one; ``block_codec.block_compressor("zstd")`` is still an unknown compression.
@@ -42,6 +45,13 @@ FLAG_SINGLE_SEGMENT, FLAG_CHECKSUM, FLAG_CONTENT_SIZE = 1, 2, 4
 # the encoder's options word: per-block table modes, repeat-offset codes, both
 ENC_TABLES, ENC_REPEAT = N.RPP_ZSTD_ENC_TABLES, N.RPP_ZSTD_ENC_REPEAT
 ENC_ADAPTIVE = ENC_TABLES | ENC_REPEAT
+LONG_MAX_BLOCK = N.RPP_ZSTD_LONG_MAX_BLOCK  # a block's largest size with long=1
+
+
+def check_long(long: int) -> int:
+    if int(long) not in (0, 1):
+        raise ValueError(f"unknown zstd long mode: {long}")
+    return int(long)
 
 
 class FrameInfo(NamedTuple):
@@ -178,28 +188,42 @@ def bound(n: int) -> int:
     return int(N.lib().rpp_zstd_bound(int(n)))
 
 
-def host_encode(data: bytes, options: int = 0, search: int = 0):
-    """``rpp_zstd_host_encode_search``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
+def host_encode(data: bytes, options: int = 0, search: int = 0, long: int = 0):
+    """``rpp_zstd_host_encode_long``: (the frame, the ratio flag): the bytes the kernels write, on the CPU."""
     src = np.frombuffer(bytes(data) + b"\0", np.uint8)
     cap = bound(len(src) - 1)
     out = np.zeros(cap, np.uint8)
     n, flag = C.c_uint64(), C.c_uint32()
-    _raise_status(N.lib().rpp_zstd_host_encode_search(src.ctypes.data_as(C.c_void_p), len(src) - 1, int(options),
-                                                      int(search), out.ctypes.data_as(C.c_void_p), cap, C.byref(n),
-                                                      C.byref(flag)))
+    _raise_status(N.lib().rpp_zstd_host_encode_long(src.ctypes.data_as(C.c_void_p), len(src) - 1, int(options),
+                                                    int(search), int(long), out.ctypes.data_as(C.c_void_p), cap,
+                                                    C.byref(n), C.byref(flag)))
     return out[:n.value].tobytes(), bool(flag.value)
 
 
+def host_sequences(data: bytes, search: int = 0, long: int = 0) -> np.ndarray:
+    """``rpp_zstd_host_long_sequences``: the (position, length, offset) rows that the host encoder writes the
+    frame of (search, long) from (a debug export)."""
+    src = np.frombuffer(bytes(data) + b"\0", np.uint8)
+    rows = np.zeros((len(src) // 4 + 1, 3), np.uint32)  # (matches of 4 bytes that do not overlap)
+    count = C.c_uint64()
+    _raise_status(N.lib().rpp_zstd_host_long_sequences(src.ctypes.data_as(C.c_void_p), len(src) - 1, int(search),
+                                                       int(long), rows.ctypes.data_as(C.c_void_p), len(rows),
+                                                       C.byref(count)))
+    return rows[:count.value].copy()
+
+
 def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
-                 stream: Optional[torch.cuda.Stream] = None, options: int = 0, search: int = 0) -> EncodedBatch:
-    """One ``rpp_zstd_encode_batch_search`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
+                 stream: Optional[torch.cuda.Stream] = None, options: int = 0, search: int = 0,
+                 long: int = 0) -> EncodedBatch:
+    """One ``rpp_zstd_encode_batch_long`` over the blocks ``d_in[in_offsets[b] : + in_sizes[b]]`` (a uint8 CUDA
     tensor; host lists of offsets and sizes): one frame per block; ``flags`` is 1 where size >= input size.
     Asynchronous on the stream."""
     dev = d_in.device
     n = len(in_sizes)
+    most = LONG_MAX_BLOCK if long else MAX_BLOCK
     for s in in_sizes:
-        if s > MAX_BLOCK:
-            raise ValueError(f"a block holds at most {MAX_BLOCK} bytes, not {s}")
+        if s > most:
+            raise ValueError(f"a block holds at most {most} bytes, not {s}")
     out_offs, cap = _layout([bound(s) for s in in_sizes])
     total = int(sum(int(s) for s in in_sizes))
     d_ioff, d_isz, d_ooff = S._i64(in_offsets, dev), S._i64(list(in_sizes), dev), S._i64(out_offs, dev)
@@ -207,21 +231,22 @@ def encode_batch(d_in: torch.Tensor, in_offsets, in_sizes: Sequence[int],
     sizes = torch.zeros(n, dtype=torch.int64, device=dev)
     flags = torch.zeros(n, dtype=torch.int32, device=dev)
     status = torch.zeros(n, dtype=torch.int32, device=dev)
-    ws_bytes = int(N.lib().rpp_zstd_encode_workspace_bytes(total, n))
+    ws_bytes = int(N.lib().rpp_zstd_encode_workspace_bytes_long(total, n, int(long)))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    _raise_status(N.lib().rpp_zstd_encode_batch_search(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, int(options),
-                                                       int(search), _ptr(out), _ptr(d_ooff), _ptr(sizes), _ptr(flags),
-                                                       _ptr(status), total, _ptr(ws), ws_bytes, _stream_ptr(stream)))
+    _raise_status(N.lib().rpp_zstd_encode_batch_long(_ptr(d_in), _ptr(d_ioff), _ptr(d_isz), n, int(options),
+                                                     int(search), int(long), _ptr(out), _ptr(d_ooff), _ptr(sizes),
+                                                     _ptr(flags), _ptr(status), total, _ptr(ws), ws_bytes,
+                                                     _stream_ptr(stream)))
     return EncodedBatch(out, d_ooff, sizes, flags, status, d_in, d_ioff, d_isz)
 
 
 class ZstdBlockCompressor:
     """``zstd_block_compressor`` (src/compression/zstd.cpp:320-441).  ``level`` (at most 22, ZSTD_maxCLevel) is
     recorded and does not change the search.  ``options`` is the encoder's options word (``ENC_TABLES``,
-    ``ENC_REPEAT``, ``ENC_ADAPTIVE``), ``search`` the search word (``depth | SEARCH_LAZY``); 0 and 0 write the bytes
-    pinned in tests/golden/zstd_enc_kat.json."""
+    ``ENC_REPEAT``, ``ENC_ADAPTIVE``), ``search`` the search word (``depth | SEARCH_LAZY``), ``long`` the long word (0 or 1);
+    0, 0 and 0 write the bytes pinned in tests/golden/zstd_enc_kat.json."""
 
-    def __init__(self, level: int = 22, device="cuda", options: int = 0, search: int = 0):
+    def __init__(self, level: int = 22, device="cuda", options: int = 0, search: int = 0, long: int = 0):
         if int(level) > 22:
             raise RuntimeError(f"invalid option(s) for zstd: level={level}")
         if int(options) & ~ENC_ADAPTIVE:
@@ -230,15 +255,17 @@ class ZstdBlockCompressor:
         self.device = torch.device(device)
         self.options = int(options)
         self.search = check_search(search)
+        self.long = check_long(long)
 
     def clone(self) -> "ZstdBlockCompressor":
-        return ZstdBlockCompressor(self.level, self.device, self.options, self.search)
+        return ZstdBlockCompressor(self.level, self.device, self.options, self.search, self.long)
 
     def type(self) -> int:
         return COMPRESSION_TYPE_ZSTD
 
     def describe(self) -> str:
-        return f"zstd [level={self.level}]"  # zstd.cpp:329-331
+        # zstd.cpp:329-331 (which does not show its `long`; this one does)
+        return f"zstd [level={self.level}, long]" if self.long else f"zstd [level={self.level}]"
 
     def metadata_requirements(self) -> str:
         return ""
@@ -251,7 +278,8 @@ class ZstdBlockCompressor:
 
     def _encode(self, blocks: Sequence[bytes]) -> EncodedBatch:
         d_in, offs = _upload(blocks, self.device)
-        return encode_batch(d_in, offs, [len(b) for b in blocks], options=self.options, search=self.search)
+        return encode_batch(d_in, offs, [len(b) for b in blocks], options=self.options, search=self.search,
+                            long=self.long)
 
     def compress(self, data: bytes, metadata: Optional[str] = None) -> bytes:
         out = self.compress_many([data], metadata, keep_bad=True)[0]
@@ -266,7 +294,7 @@ class ZstdBlockCompressor:
         if not blocks:
             return []
         if self.device.type == "cpu":  # the host restatement: the kernels' bytes without a GPU
-            frames, flags = zip(*(host_encode(b, self.options, self.search) for b in blocks))
+            frames, flags = zip(*(host_encode(b, self.options, self.search, self.long) for b in blocks))
         else:
             res = self._encode(blocks)
             torch.cuda.current_stream().synchronize()
@@ -312,13 +340,29 @@ class ZstdBlockCompressor:
 
 def block_compressor(spec: str, device="cuda") -> ZstdBlockCompressor:
     """The factory for ``zstd[:level=N][:depth=N][:lazy=0|1]``; any other option raises ``invalid option(s) for
-    zstd: ...``.  ``depth`` and ``lazy`` make the search word; ``level`` maps to none."""
+    zstd: ...``, ``long`` among them (:func:`block_compressor_long` takes it).  ``depth`` and ``lazy`` make the
+    search word; ``level`` maps to none."""
+    return _from_spec(spec, device, False)
+
+
+def block_compressor_long(spec: str, device="cuda") -> ZstdBlockCompressor:
+    """The factory for ``zstd[:level=N][:long[=0|1]][:depth=N][:lazy=0|1]``: :func:`block_compressor` with the
+    reference's ``long`` option (a flag, as in its option map: alone it means 1), which makes the long word."""
+    return _from_spec(spec, device, True)
+
+
+def _from_spec(spec: str, device, with_long: bool) -> ZstdBlockCompressor:
     name, *opts = spec.split(":")
     if name != "zstd":
         raise RuntimeError(f"unknown compression: {name}")
-    level = [22]
+    level, long = [22], [0]
+    if with_long:
+        opts = ["long=1" if opt == "long" else opt for opt in opts]
 
-    def take_level(key, value):
+    def take(key, value):
+        if with_long and key == "long" and value in ("0", "1"):
+            long[0] = int(value)
+            return True
         try:
             if key != "level" or int(value) > 22:
                 return False
@@ -327,5 +371,5 @@ def block_compressor(spec: str, device="cuda") -> ZstdBlockCompressor:
         level[0] = int(value)
         return True
 
-    search = spec_search(opts, "zstd", take_level)
-    return ZstdBlockCompressor(level[0], device, search=search)
+    search = spec_search(opts, "zstd", take)
+    return ZstdBlockCompressor(level[0], device, search=search, long=long[0])

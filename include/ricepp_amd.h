@@ -1193,6 +1193,48 @@ int rpp_incompressible_host_scan(const uint8_t* in, const uint64_t* in_offsets, 
                                  uint32_t* verdicts, uint64_t* totals, uint64_t* frag_rows, uint32_t* frag_count,
                                  int32_t* status);
 
+/*
+ * Long-distance matching for the Zstandard encoder: a third opt-in word beside `options` and `search`, the mirror
+ * of the reference's `long` option (src/compression/zstd.cpp:69, :404-406).  long_mode 0 is the *_search call:
+ * the same kernels, the same launches, the same bytes.  long_mode 1 adds matches of at least 64 bytes against
+ * anything earlier in the same block (a table of the first occurrence of every 32-byte window on a 32-byte grid),
+ * merged with the short search's sequences; a block then holds at most RPP_ZSTD_LONG_MAX_BLOCK bytes, and a larger
+ * one has the status of an over-size block.  Any other long_mode is RPP_INVALID_ARGUMENT.  LZ4 cannot express
+ * these offsets and has no such word.  The complete definition is at the top of
+ * dwarfs_amd/csrc/zstd_long_host.cpp.  Frames are stock RFC 8878 with a window of the block's size; rpp_zstd_bound,
+ * flags, statuses and every other part of the contracts are those of the *_search calls.  The workspace of the
+ * batch calls is rpp_zstd_encode_workspace_bytes_long(total_bytes, nblocks, long_mode) bytes (with long_mode 0
+ * rpp_zstd_encode_workspace_bytes), that of the scan rpp_incompressible_workspace_bytes_long.
+ * rpp_zstd_host_long_sequences is a debug export of the host side: the (position, length, offset) triples, three
+ * uint32 each, that the frame of (search, long_mode) is written from; *count gets their number, and a capacity
+ * (in triples) below it is RPP_OUTPUT_TOO_SMALL.
+ */
+#define RPP_ZSTD_LONG_MAX_BLOCK (UINT64_C(1) << 27)
+uint64_t rpp_zstd_encode_workspace_bytes_long(uint64_t total_bytes, uint32_t nblocks, uint32_t long_mode);
+int rpp_zstd_encode_batch_long(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                               uint32_t nblocks, uint32_t options, uint32_t search, uint32_t long_mode, uint8_t* d_out,
+                               const uint64_t* d_out_offsets, uint64_t* d_out_bytes, uint32_t* d_flags,
+                               int32_t* d_status, uint64_t total_bytes, void* d_workspace, uint64_t workspace_bytes,
+                               void* stream);
+int rpp_zstd_host_encode_long(const uint8_t* in, uint64_t n, uint32_t options, uint32_t search, uint32_t long_mode,
+                              uint8_t* out, uint64_t capacity, uint64_t* out_bytes, uint32_t* bad_ratio);
+int rpp_zstd_host_long_sequences(const uint8_t* in, uint64_t n, uint32_t search, uint32_t long_mode,
+                                 uint32_t* triples, uint64_t capacity, uint64_t* count);
+uint64_t rpp_incompressible_workspace_bytes_long(uint64_t total_bytes, uint32_t npieces, uint32_t nextents,
+                                                 uint32_t long_mode);
+int rpp_incompressible_scan_batch_long(const uint8_t* d_in, const uint64_t* d_in_offsets, const uint64_t* d_in_bytes,
+                                       uint32_t npieces, const uint32_t* d_piece_base, uint32_t nextents,
+                                       double max_ratio, uint32_t generate_fragments, uint32_t options,
+                                       uint32_t search, uint32_t long_mode, uint64_t* d_sizes, uint32_t* d_verdicts,
+                                       uint64_t* d_totals, uint64_t* d_frag_rows, uint32_t* d_frag_count,
+                                       int32_t* d_status, uint64_t total_bytes, void* d_workspace,
+                                       uint64_t workspace_bytes, void* stream);
+int rpp_incompressible_host_scan_long(const uint8_t* in, const uint64_t* in_offsets, const uint64_t* in_bytes,
+                                      uint32_t npieces, const uint32_t* piece_base, uint32_t nextents, double max_ratio,
+                                      uint32_t generate_fragments, uint32_t options, uint32_t search,
+                                      uint32_t long_mode, uint64_t* sizes, uint32_t* verdicts, uint64_t* totals,
+                                      uint64_t* frag_rows, uint32_t* frag_count, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,9 @@ GIB = float(1 << 30)
 MIB = 1 << 20
 KERNELS = ("rpp_lz4_prep_kernel", "rpp_lz4_search_kernel", "rpp_zstd_enc_entropy_kernel", "rpp_zstd_enc_place_kernel",
            "rpp_zstd_enc_emit_kernel")
+# with --long 1 the long-distance matcher's kernels (csrc/zstd_long.hip) are listed as well
+LONG_KERNELS = ("rpp_zstd_long_prepare_kernel", "rpp_zstd_long_index_kernel", "rpp_zstd_long_find_kernel",
+                "rpp_zstd_long_merge_kernel")
 
 
 def main():
@@ -47,6 +50,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--options", type=int, nargs="+", default=[0])
     ap.add_argument("--search", type=lambda v: int(v, 0), nargs="+", default=[0])
+    ap.add_argument("--long", type=int, nargs="+", default=[0], help="the long word: 0, 1 or both; 1 adds a row per "
+                    "shape with \"long\": 1 and one batch of 16 MiB blocks, the workload's own block size")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "zstd_encode.jsonl"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "zstd_encode_bench needs a GPU"
@@ -60,6 +65,8 @@ def main():
         ("skewed_64KiB_x1024", [EC.skewed(7003, 65536)] * 1024),
         ("every_test_input", [d for _, d in EC.inputs()]),
     )
+    if 1 in args.long:  # half of every block repeats its other half, 8 MiB back
+        shapes += (("half_repeat_16MiB_x4", [EC.skewed(7004 + i, 8 * MIB) * 2 for i in range(4)]),)
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     rows = []
     for shape, blocks in shapes:
@@ -68,12 +75,13 @@ def main():
         d_in, in_offs = _upload(blocks, dev)
         arrays = [S._i64(in_offs, dev), S._i64(sizes, dev)]
         results = {}
-        codecs = [(("zstd", o, w), Z.bound, N.lib().rpp_zstd_encode_workspace_bytes,
-                   lambda *a, o=o, w=w: N.lib().rpp_zstd_encode_batch_search(*a[:4], o, w, *a[4:]))
-                  for o in args.options for w in args.search]
-        codecs += [(("lz4", 0, w), lz4.bound, N.lib().rpp_lz4_encode_workspace_bytes,
+        codecs = [(("zstd", o, w, g), Z.bound,
+                   lambda total, n, g=g: N.lib().rpp_zstd_encode_workspace_bytes_long(total, n, g),
+                   lambda *a, o=o, w=w, g=g: N.lib().rpp_zstd_encode_batch_long(*a[:4], o, w, g, *a[4:]))
+                  for o in args.options for w in args.search for g in args.long]
+        codecs += [(("lz4", 0, w, 0), lz4.bound, N.lib().rpp_lz4_encode_workspace_bytes,
                     lambda *a, w=w: N.lib().rpp_lz4_encode_batch_search(*a[:4], w, *a[4:])) for w in args.search]
-        for (codec, options, search), bound, ws_of, call_of in codecs:
+        for (codec, options, search, long), bound, ws_of, call_of in codecs:
             out_offs, cap = _layout([bound(s) for s in sizes])
             out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
             d_ooff = S._i64(out_offs, dev)
@@ -111,24 +119,24 @@ def main():
                         for _ in range(args.iters):
                             call()
                         torch.cuda.synchronize()
-                    found = {}
+                    found, wanted = {}, KERNELS + (LONG_KERNELS if long else ())
                     for e in prof.key_averages():
-                        for k in KERNELS:
+                        for k in wanted:
                             if k in e.key.replace("rpp_lz4_deep_search_kernel", "rpp_lz4_search_kernel"):
                                 us = getattr(e, "device_time_total", None)
                                 if us is None:
                                     us = e.cuda_time_total
                                 found[k] = us / 1e6 / args.iters
-                    kernels = found if len(found) == len(KERNELS) else None
+                    kernels = found if len(found) == len(wanted) else None
                 except Exception as e:  # the trace is an extra: the row stands without it
                     print(f"no kernel trace: {e}", file=sys.stderr)
-            results[codec, options, search] = (a.elapsed_time(b) / 1e3 / args.iters, int(out_sizes.sum().item()), ws_bytes, kernels)
+            results[codec, options, search, long] = (a.elapsed_time(b) / 1e3 / args.iters, int(out_sizes.sum().item()), ws_bytes, kernels)
             del out, ws
-        for o, w in ((o, w) for o in args.options for w in args.search):
-            t_lz4, lz4_bytes, _, _ = results["lz4", 0, w]
-            t, frame_bytes, ws_bytes, kernels = results["zstd", o, w]
+        for o, w, g in ((o, w, g) for o in args.options for w in args.search for g in args.long):
+            t_lz4, lz4_bytes, _, _ = results["lz4", 0, w, 0]
+            t, frame_bytes, ws_bytes, kernels = results["zstd", o, w, g]
             rows.append({"what": "encode", "device": torch.cuda.get_device_name(0), "shape": shape, "options": o,
-                         "search": w,
+                         "search": w, "long": g,
                          "blocks": n, "input_bytes": total, "frame_bytes": frame_bytes, "lz4_bytes": lz4_bytes,
                          "workspace_bytes": ws_bytes, "iters": args.iters, "seconds": t, "gib_per_s": total / GIB / t,
                          "kernels_seconds": kernels, "lz4_seconds": t_lz4, "lz4_gib_per_s": total / GIB / t_lz4,
