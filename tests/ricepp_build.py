@@ -87,6 +87,8 @@ class Case(NamedTuple):
     status: int
     mis: int = 0                 # the byte offset mod 4 the stream is to be packed at
     in_bytes: Optional[int] = None  # the size the decoder is offered (None: len(stream))
+    inp: Optional[np.ndarray] = None  # encode cases: the input samples where they are not ``want`` (dropped dirt)
+    fields: Optional[Fields] = None   # encode cases: the fields the stream was built from
 
     @property
     def size(self) -> int:
@@ -763,3 +765,748 @@ def decoys() -> List[Case]:
 
 FAMILIES = {"density": density, "window_edges": window_edges, "long_runs": long_runs, "class_pairs": class_pairs,
             "values": values, "end_of_input": end_of_input, "decoys": decoys}
+
+
+# ===============================================================================================================
+# The encode side: streams an encoder writes, built from zig-zag deltas and a declared kind per sub-block
+# ===============================================================================================================
+#
+# ``from_deltas`` turns zig-zag deltas and a kind per sub-block into ``Fields`` by the obvious loop (q = d >> fs,
+# r = d & mask; a raw sub-block stores its pixels as they lie; a zero sub-block has no delta but 0).  ``split_rule``
+# restates compute_best_split (encode.h:43-90) and ``wave_groups`` / ``flush_trace`` / ``seg_chunks_rule`` the
+# encode kernels' geometry: like the decode geometry above they are used only to aim the cases and to count what a
+# family reaches, never to compute an expected byte.  The expected bytes of every case are ``build(cfg, fields)``;
+# that an encoder writes exactly these is proved on the CPU against the oracle and the compiled reference by
+# tests/test_ricepp_encode_constructed_host.py.
+#
+# What the split rule can and cannot do (with avg = sum / n, start = max(0, bit_width(floor(avg)) - 2), so
+# 2^(start+1) <= avg < 2^(start+2) unless start was clamped to 0, and x_i = d_i / 2^f):
+#   * no step down: cost(f-1) <= cost(f) needs sum(floor(2x) - floor(x)) <= n, but floor(2x) - floor(x) >= x - 1/2
+#     and at f = start the x sum to 2n or more, so the sum is at least 1.5 n.  A walk of direction -1 stays at
+#     `start` (and with start 0 nothing lies below).
+#   * at most one step up behind the first pair: at f = start + 1 the x sum to less than 2n and
+#     floor(x) - floor(x/2) <= (x + 1) / 2, so one step (to start + 2) can be an equal or a lower cost; at
+#     f = start + 2 the same sum is below x/4 + 1/2 each, less than n in all.
+#   * fs < 14 implies bits < 16 n: the chosen fs is start, start + 1 or start + 2 and at each of them
+#     sum(d >> fs) < 2n where fs is 12 or 13 (else bits < n (fs + 5) <= 16 n).  So raw is only ever reached
+#     through fs 14 and 15, i.e. starts 12 (equal-cost step 13 -> 14), 13 and 14.
+#   * the hill climb never ends above the lowest cost of any fs: cost(f + 1) - cost(f) = n - sum(g(x_i)) with
+#     g(x) = floor(x) - floor(x / 2) = ceil(floor(x) / 2), and g(x / 2) <= g(x), so the cost is convex in fs and a
+#     local minimum is the global one.  (A writer that takes the global minimum differs only in which of several
+#     fs of equal cost it takes.)
+# The host test asserts all four on every sub-block of every family.
+
+ENC_WIN_WORDS = 1024      # ricepp_encode.hip kEncWin
+ENC_FLUSH_WORDS = 256     # kEncFlushWords
+ENC_SEG_MIN, ENC_SEG_MAX, ENC_TARGET_UNITS = 16, 256, 2048  # kEncSegChunksMin, kEncSegChunks, kEncTargetUnits
+
+
+def enc_template(bs: int) -> Tuple[int, int]:
+    """(SPL, G) of enc_kernel_for: samples per lane, lanes per sub-block."""
+    spl = 16 if bs > 64 else 8
+    m, g = -(-bs // spl), 1
+    while g < m:
+        g *= 2
+    return spl, g
+
+
+def seg_chunks_rule(total_samples: int, cfg: Cfg) -> int:
+    """enc_seg_chunks: chunks per unit for a batch of total_samples."""
+    chunks, c = total_samples // (cfg.bs * cfg.cs), ENC_SEG_MAX
+    while c > ENC_SEG_MIN and chunks // c < ENC_TARGET_UNITS:
+        c >>= 1
+    return c
+
+
+def zz(delta: int) -> int:
+    """The zig-zag code of a signed 16-bit difference (encode.h:119)."""
+    assert -32768 <= delta <= 32767
+    return (delta << 1) if delta >= 0 else ((-delta << 1) - 1)
+
+
+def unzz(d: int) -> int:
+    return (d >> 1) ^ -(d & 1)
+
+
+def split_cost(d, fs: int) -> int:
+    d = np.asarray(d, np.int64)
+    return int(len(d) * (fs + 1) + (d >> fs).sum())
+
+
+class Walk(NamedTuple):
+    start: int
+    tie0: bool      # bits0 == bits1: no walk
+    dir: int
+    steps: int      # candidates taken behind the first pair
+    tie_steps: int  # of these, at an equal cost
+    fs: int
+    bits: int
+    best: int       # the lowest cost of any fs 0..15
+
+
+def split_rule(d, n_for_start: Optional[int] = None) -> Walk:
+    """compute_best_split (encode.h:43-90) restated, to aim cases only."""
+    d = np.asarray(d, np.int64)
+    n, total = len(d), int(d.sum())
+    start = max(0, (total // (n_for_start or n)).bit_length() - 2)
+    b0, b1 = split_cost(d, start), split_cost(d, start + 1)
+    cand, bits, direction = (start + 1, b1, 1) if b1 <= b0 else (start, b0, -1)
+    steps = ties = 0
+    if b0 != b1:
+        while 0 < cand < 14:
+            t = split_cost(d, cand + direction)
+            if t > bits:
+                break
+            ties += t == bits
+            bits, cand, steps = t, cand + direction, steps + 1
+    return Walk(start, b0 == b1, direction, steps, ties, cand, bits, min(split_cost(d, f) for f in range(16)))
+
+
+def aim_kind(d):
+    """"zero", "raw" or the fs an encoder takes for these deltas, by the restated rule."""
+    if not int(np.asarray(d, np.int64).sum()):
+        return "zero"
+    w = split_rule(d)
+    return w.fs if w.fs < 14 and w.bits < 16 * len(d) else "raw"
+
+
+def stored(cfg: Cfg, px: int, dirt: int = 0) -> int:
+    t = (((px & 0xFFFF) << cfg.ulsb) & 0xFFFF) | dirt
+    return _bswap(t) if cfg.big else t
+
+
+def from_deltas(cfg: Cfg, first_px: Sequence[int], subs, dirt=None):
+    """(Fields, input samples) of sub-blocks given as (kind, zig-zag deltas) in stream order; kind is "zero",
+    "raw" or fs.  The running pixel of a component starts at first_px (the stream's initial value: its first
+    delta is 0, codec.h:72) and, with ulsb > 0, stays inside [0, 2^(16 - ulsb)).  ``dirt`` maps a sub-block's
+    index to unused low bits per sample: a raw sub-block stores them as they lie, in a zero sub-block they are in
+    the input only (the encoder drops them)."""
+    top = 1 << (16 - cfg.ulsb)
+    px = list(first_px)
+    seen = [False] * cfg.cs
+    out, dirty = [], {}
+    pos = 0
+    for i, (kind, d) in enumerate(subs):
+        c = i % cfg.cs
+        d = [int(x) for x in d]
+        if not seen[c]:
+            assert d[0] == 0 and 0 <= px[c] < top, "a component's first sample is its own reference"
+            seen[c] = True
+        low = list(dirt[i]) if dirt and i in dirt else [0] * len(d)
+        assert all(0 <= x < (1 << cfg.ulsb) for x in low)
+        vals = []
+        for x in d:
+            assert 0 <= x <= 0xFFFF
+            p = px[c] + unzz(x)
+            assert cfg.ulsb == 0 or 0 <= p < top, "the pixel leaves its range: not what a 16-bit difference sees"
+            px[c] = p & 0xFFFF
+            vals.append(px[c])
+        if kind == "zero":
+            assert not any(d)
+            out.append(Zero(len(d)))
+            if any(low):
+                dirty[i] = [stored(cfg, v, l) for v, l in zip(vals, low)]
+        elif kind == "raw":
+            out.append(Raw(tuple(stored(cfg, v, l) for v, l in zip(vals, low))))
+        else:
+            assert not any(low)
+            out.append(Rice(kind, tuple((x >> kind, x & ((1 << kind) - 1)) for x in d)))
+        pos += len(d)
+    f = Fields(tuple(first_px), tuple(out))
+    inp = expand(cfg, f)
+    if dirty:  # the input of a dirty zero sub-block: sample j of sub-block i lies at chunk base + comp + cs * j
+        inp = inp.copy()
+        base = 0
+        for g in range(0, len(out), cfg.cs):
+            for c in range(cfg.cs):
+                if g + c in dirty:
+                    inp[base + c:base + cfg.cs * count(out[g]):cfg.cs] = dirty[g + c]
+            base += cfg.cs * count(out[g])
+    return f, inp
+
+
+def enc_case(what: str, cfg: Cfg, first_px, dsubs, kinds=None, dirt=None) -> Case:
+    """A case from deltas; kinds default to what the restated rule aims at (the host test proves them)."""
+    kinds = kinds or [aim_kind(d) for d in dsubs]
+    f, inp = from_deltas(cfg, first_px, list(zip(kinds, dsubs)), dirt)
+    want = expand(cfg, f)
+    return Case(what, cfg, build(cfg, f), len(want), want, OK, 0, None, None if inp is want else inp, f)
+
+
+def deltas_of(cfg: Cfg, c: Case) -> List[np.ndarray]:
+    """The zig-zag deltas of each sub-block of a case's input, in stream order: pixel differences mod 2^16."""
+    inp = c.want if c.inp is None else c.inp
+    px = np.array([px_read(cfg, int(v)) for v in inp], np.int64)
+    out, last = [], [int(v) for v in c.fields.init]
+    base = 0
+    for g in range(0, len(c.fields.subs), cfg.cs):
+        cnt = count(c.fields.subs[g])
+        for k in range(cfg.cs):
+            p = px[base + k:base + cfg.cs * cnt:cfg.cs]
+            diff = (np.diff(np.concatenate(([last[k]], p))) + 32768) % 65536 - 32768
+            out.append(np.where(diff >= 0, diff << 1, (-diff << 1) - 1))
+            last[k] = int(p[-1])
+        base += cfg.cs * cnt
+    return out
+
+
+def sub_bits(s: Sub) -> int:
+    if isinstance(s, Zero):
+        return 4
+    if isinstance(s, Raw):
+        return 4 + 16 * len(s.values)
+    return 4 + sum(q for q, _ in s.codes) + len(s.codes) * (1 + s.fs)
+
+
+def ones(n: int, s: int, skip_first: bool = True) -> List[int]:
+    """n deltas of 0 and 1 with s ones, 0 < s < n: an encoder takes fs 0 (start 0, n + s < 2n), 4 + n + s bits."""
+    assert 0 < s < n
+    d = [0] * n
+    for j in range(s):
+        d[n - 1 - j] = 1
+    return d
+
+
+def dial(cfg: Cfg, nchunks: int, extra: int, rng=None) -> List[List[int]]:
+    """Deltas of nchunks full chunks that take 4 * cs * nchunks + extra bits: zero sub-blocks, fs 0 sub-blocks of
+    zeros and ones (n + s bits more, 0 < s < n) and raw sub-blocks (16 n bits more, noise from rng)."""
+    n, slots = cfg.bs, cfg.cs * nchunks
+    subs = [[0] * n for _ in range(slots)]
+    at = slots - 1
+    while rng is not None and extra >= 16 * n + (2 * n + 2) or extra == 16 * n:
+        subs[at] = [0] + [int(x) for x in rng.integers(0x7000, 0xFFFF, n - 1)]
+        extra -= 16 * n
+        at -= 1
+    if extra:
+        b = max(1, -(-extra // (2 * n - 1)))
+        assert b * (n + 1) <= extra <= b * (2 * n - 1) and b <= at + 1, (cfg, nchunks, extra)
+        for j in range(b):
+            s = (extra - b * n) // b + (j < (extra - b * n) % b)
+            subs[at - j] = ones(n, s)
+    return subs
+
+
+def noise(rng, n: int) -> List[int]:
+    """Deltas an encoder stores raw (start 13 or 14)."""
+    return [int(x) for x in rng.integers(0x9000, 0xFFFF, n)]
+
+
+def wave_groups(cfg: Cfg, f: Fields, lo: int = 0, hi: Optional[int] = None):
+    """The sub-blocks one wave takes per iteration (64 / G of them), as index lists."""
+    spw = 64 // enc_template(cfg.bs)[1]
+    hi = len(f.subs) if hi is None else hi
+    return [list(range(s, min(s + spw, hi))) for s in range(lo, hi, spw)]
+
+
+def flush_trace(cfg: Cfg, f: Fields):
+    """(complete words since the last flush after each iteration, flushes) of a one-wave encode: enc_flush
+    streams out when F = (base >> 5) & ~15 reaches win_w0 + 256 words."""
+    base, w0, words, flushes = 16 * cfg.cs, 0, [], 0
+    for grp in wave_groups(cfg, f):
+        base += sum(sub_bits(f.subs[i]) for i in grp)
+        words.append((base >> 5) - w0)
+        assert words[-1] < ENC_WIN_WORDS - 1
+        F = (base >> 5) & ~15
+        if F >= w0 + ENC_FLUSH_WORDS:
+            w0, flushes = F, flushes + 1
+    return words, flushes
+
+
+def segments_of(cfg: Cfg, f: Fields, segc: int = ENC_SEG_MIN):
+    """(offsets o_k, lengths L_k in bits) of the units a stream of more than segc chunks is split into."""
+    n = len(f.subs) // cfg.cs
+    if n <= segc:
+        return [0], [16 * cfg.cs + sum(sub_bits(s) for s in f.subs)]
+    L = []
+    for lo in range(0, n, segc):
+        L.append(sum(sub_bits(s) for s in f.subs[lo * cfg.cs:(lo + segc) * cfg.cs]) + (16 * cfg.cs if lo == 0 else 0))
+    return [sum(L[:k]) for k in range(len(L))], L
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_split_start
+# ---------------------------------------------------------------------------------------------------------------
+
+START_BS_ALL = (16, 29)          # every n in 1..bs
+START_BS_SOME = (128, 200, 500)  # n in {1, 2, 3, 7, 8, 9, bs - 1, bs}
+
+
+def start_ns(bs: int) -> List[int]:
+    return list(range(1, bs + 1)) if bs in START_BS_ALL else [1, 2, 3, 7, 8, 9, bs - 1, bs]
+
+
+@functools.lru_cache(maxsize=None)
+def enc_split_start() -> List[Case]:
+    """A zero chunk, then one sub-block of n deltas 2^m (m = 0..13) per component, one of them lowered by 1, left
+    or raised by 1: sums n 2^m - 1, n 2^m, n 2^m + 1.  With all deltas 2^m the costs at m - 1 and m are equal,
+    the walk stops at start + 1 and the chosen fs max(m, 1) reveals `start`.  n < bs is the ragged last chunk.
+    The second component of a cs 2 stream runs m + 5 and the next variant."""
+    out = []
+    i = 0
+    for bs in START_BS_ALL + START_BS_SOME:
+        for n in start_ns(bs):
+            for m in range(14):
+                for var in (-1, 0, 1):
+                    cfg = Cfg(bs, 1 + i % 2, i % 4 < 2, 0)
+                    i += 1
+                    subs = [[0] * bs] * cfg.cs
+                    for c in range(cfg.cs):
+                        mc, vc = (m + 5 * c) % 14, (var + 1 + c) % 3 - 1
+                        d = [1 << mc] * n
+                        d[n // 2] += vc
+                        subs.append(d)
+                    out.append(enc_case(f"start bs={bs} n={n} m={m} var={var:+d} cs={cfg.cs} {'be' if cfg.big else 'le'}",
+                                        cfg, (0x4000 + i,) * cfg.cs, subs))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_split_walk
+# ---------------------------------------------------------------------------------------------------------------
+
+WALK_BS = (16, 64, 128)
+
+
+def _walk_subs(bs: int):
+    """[(label, deltas)]: every walk the rule can take."""
+    rng = np.random.default_rng(4300 + bs)
+    out = []
+
+    def mix(lo_hi_share):
+        d = []
+        for (lo, hi), share in lo_hi_share:
+            d += [int(x) for x in rng.integers(lo, hi, max(1, round(share * bs)))]
+        d = (d + [d[-1]] * bs)[:bs]
+        return [d[j] for j in rng.permutation(bs)]
+
+    for f in range(1, 14):
+        s = f - 1  # the start aimed at
+        out.append((f"tie_step start={s}", mix([((1 << f, 2 << f), 1.0)])))                  # start+1, = cost, start+2
+        out.append((f"strict_step start={s}", mix([((1 << f, (1 << f) + 1), 0.6), ((3 << f, (3 << f) + 1), 0.4)])))
+        out.append((f"down start={s + 1}", mix([(((1 << f) * 2 - 2, (1 << f) * 2), 0.49),    # direction -1 at start
+                                                 (((3 << f) * 2 - 2, (3 << f) * 2), 0.51)])))
+        out.append((f"plain start={s}", mix([((0, 2 << f), 1.0)])))
+    out.append(("start0 down", mix([((0, 1), 0.7), ((1, 2), 0.3)])))
+    out.append(("start0 up", mix([((1, 4), 1.0)])))
+    # into fs 14 and 15
+    out.append(("13->14 by an equal-cost step from start 12", mix([((1 << 13, 1 << 14), 1.0)])))
+    out.append(("14 at the first pair from start 13, equal", mix([((1 << 14, 3 << 13), 1.0)])))
+    out.append(("14 at the first pair from start 13, lower", mix([((3 << 13, 1 << 15), 1.0)])))
+    out.append(("13 kept from start 13", mix([((0x1F00, 0x2000), 0.45), ((0x5F00, 0x6000), 0.55)])))
+    out.append(("15 at the first pair from start 14, equal", [0x8000] * bs))
+    out.append(("15 at the first pair from start 14, lower", mix([((0xC000, 0x10000), 1.0)])))
+    out.append(("14 kept from start 14", mix([((0x3F00, 0x4000), 0.3), ((0xBF00, 0xC000), 0.7)])))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def enc_split_walk_fields():
+    out = []
+    for bs in WALK_BS:
+        subs = _walk_subs(bs)
+        for cs in (1, 2):
+            per = 6 * cs
+            for k in range(0, len(subs), per):
+                part = subs[k:k + per]
+                part = part + part[:(-len(part)) % cs]
+                cfg = Cfg(bs, cs, (k // per) % 2 == 0, 0)
+                dsubs = [[0] * bs] * cs + [d for _, d in part]
+                out.append((f"walk bs={bs} cs={cs} #{k // per}", cfg, dsubs, [l for l, _ in part]))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def enc_split_walk() -> List[Case]:
+    """Every walk the split rule can take (see the note above): direction -1 and +1 at the first pair, one more
+    step at a lower and at an equal cost, fs 13 reached and kept, fs 14 from starts 12, 13 and 14 and fs 15 from
+    start 14 (raw)."""
+    return [enc_case(what, cfg, (0x2000 + 7 * i,) * cfg.cs, dsubs)
+            for i, (what, cfg, dsubs, _) in enumerate(enc_split_walk_fields())]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_emit_paths
+# ---------------------------------------------------------------------------------------------------------------
+
+EMIT_FULL = (8, 16, 32, 64, 128, 256, 512)  # bs == G * SPL: every lane full
+EMIT_RAGGED = (29, 200)                     # SPL 8 and SPL 16 with empty lanes: the per-sample path
+EMIT_T = (31, 32, 33, 34)                   # 2k + q of the largest odd-sample run
+
+
+def _emit_target(rng, bs: int, fs: int, T: int):
+    """A sub-block an encoder codes at fs whose largest odd-sample run is T - 2 (fs + 1), in one sample."""
+    k = fs + 1
+    q = T - 2 * k
+    for _ in range(400):
+        base = int(rng.integers(max(0, fs - 1), fs + 2))
+        d = [int(x) for x in rng.integers(0, 2 << base, bs)] if bs > 1 else [0]
+        at = 2 * int(rng.integers(0, bs // 2)) + 1
+        d[at] = (q << fs) | int(rng.integers(0, 1 << fs))
+        if d[at] > 0xFFFF or aim_kind(d) != fs:
+            continue
+        if sum(1 for j in range(1, bs, 2) if d[j] >> fs >= q) == 1:
+            return d, at
+    return None
+
+
+def _emit_long_even(rng, bs: int, fs: int):
+    """A sub-block coded at fs with an even-sample run of 1000 zeros or more and no odd run: the other deltas lie
+    below 2^fs, so the average is about 2.5 * 2^fs (start = fs) and the run's ceil(q / 2) < n keeps the first
+    pair from going up.  That needs n > 500: bs 512 only."""
+    d = [int(x) for x in rng.integers(0, 1 << fs, bs)]
+    at = 2 * int(rng.integers(0, bs // 2))
+    d[at] = (int(rng.integers(1000, 1022)) << fs) | d[at]
+    return d if aim_kind(d) == fs else None
+
+
+@functools.lru_cache(maxsize=None)
+def enc_emit_paths_fields():
+    out = []
+    for bs in EMIT_FULL + EMIT_RAGGED:
+        spw = 64 // enc_template(bs)[1]
+        for cs in ((1, 2) if bs in (16, 128, 29) else (1,)):
+            rng = np.random.default_rng(77 * bs + cs)
+            targets = []
+            for fs in range(14):
+                for T in EMIT_T:
+                    t = _emit_target(rng, bs, fs, T)
+                    if t:
+                        targets.append(((fs, T), t[0]))
+            if bs == 512:
+                for fs in range(6):
+                    d = _emit_long_even(rng, bs, fs)
+                    if d:
+                        targets.append(("long_even", d))
+            # one target per iteration of the wave, at a varying place; the other sub-blocks of the iteration are
+            # a short low-fs one (which moves the header's phase) and zero sub-blocks
+            per_stream = max(1, 4096 // (spw * bs))
+            for k in range(0, len(targets), per_stream):
+                dsubs, meta = [], []
+                for j, (label, d) in enumerate(targets[k:k + per_stream]):
+                    group = [[0] * bs for _ in range(spw)]
+                    group[0] = [0] + [int(x) for x in rng.integers(0, 4, bs - 1)]
+                    if not any(group[0]):
+                        group[0] = [0] * bs
+                    at = cs + (k + j) % (spw - cs)
+                    group[at] = d
+                    meta.append((len(dsubs) + at, label))
+                    dsubs += group
+                cfg = Cfg(bs, cs, (k // per_stream) % 2 == 0, 0)
+                out.append((f"emit bs={bs} cs={cs} #{k // per_stream}", cfg, dsubs, meta))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def enc_emit_paths() -> List[Case]:
+    """For every full-lane shape and one ragged shape per SPL, and every fs 0..13: sub-blocks whose largest
+    odd-sample run makes 2k + q 31, 32 (the pair path), 33 and 34 (the two-code path) in exactly one lane of the
+    wave, the other sub-blocks of the iteration short or zero; even-sample runs of 1000 and more beside short odd
+    ones; the headers at every bit phase mod 32."""
+    return [enc_case(what, cfg, (0x7000 + i,) * cfg.cs, dsubs)
+            for i, (what, cfg, dsubs, _) in enumerate(enc_emit_paths_fields())]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_flush_edges
+# ---------------------------------------------------------------------------------------------------------------
+
+FLUSH_WORDS = (255, 256, 257, 271, 272, 273)
+FLUSH_DIAL = ((29, 1), (29, 2))
+FLUSH_RAW = tuple((bs, cs) for bs in (8, 16, 32, 64, 128, 256, 512) for cs in (1, 2))
+
+
+def _flush_plan(cfg: Cfg, targets):
+    """Raw sub-blocks per iteration such that the complete words since the last flush are each of ``targets`` in
+    turn after some iteration, and below 255 after every iteration between."""
+    spw = 64 // enc_template(cfg.bs)[1]
+    zero_it, raw = 4 * spw, 16 * cfg.bs
+    rel, plan = 16 * cfg.cs, []
+    for W in targets:
+        hit = None
+        for k in range(1, 60):
+            for R in range(0, spw * k + 1):
+                end = rel + zero_it * k + raw * R
+                last = min(spw, R)
+                before = end - zero_it - raw * last
+                if end >> 5 == W and (k == 1 or (before >> 5 < 255 and R - last <= spw * (k - 1))):
+                    hit = (k, R, last)
+                    break
+            if hit:
+                break
+        if not hit:  # (not every count can follow every other: the next one of the list is tried)
+            continue
+        k, R, last = hit
+        rest = R - last
+        for j in range(k - 1):
+            r = min(spw, rest)
+            plan.append(r)
+            rest -= r
+        plan.append(last)
+        rel += zero_it * k + raw * R
+        F = (rel >> 5) & ~15
+        if F >= ENC_FLUSH_WORDS:
+            rel -= 32 * F
+    return plan
+
+
+@functools.lru_cache(maxsize=None)
+def enc_flush_edges() -> List[Case]:
+    """One-wave encodes whose complete words since the last flush are 255, 256, 257, 271, 272 and 273 after an
+    iteration (raw and zero sub-blocks dial the bits), at least three flushes per stream, a last ragged fs 0
+    chunk that takes the total bits to every residue mod 32; and all-raw streams (the worst case, 256 or 512
+    words per iteration) for every kernel template and cs."""
+    out = []
+    i = 0
+    for bs, cs in FLUSH_DIAL:
+        cfg = Cfg(bs, cs, True, 0)
+        spw = 64 // enc_template(bs)[1]
+        rng = np.random.default_rng(900 + bs + cs)
+        for r in range(32):
+            targets = [FLUSH_WORDS[(r + j) % 6] for j in range(6)]
+            dsubs = []
+            for raws in _flush_plan(cfg, targets):
+                dsubs += [noise(rng, bs) for _ in range(raws)] + [[0] * bs] * (spw - raws)
+            dsubs[0] = [0] + dsubs[0][1:]
+            if cs == 2:
+                dsubs[1] = [0] + dsubs[1][1:]
+            # the last chunk: n + s + 4 cs more bits, the total at residue r
+            have = 16 * cs + sum(4 + 16 * bs * any(d) for d in dsubs) + 4 * cs
+            t = 16 + (r - have - 16) % 32  # n + s
+            n = t // 2 + 1
+            s = t - n
+            dsubs += [ones(n, s)] + [[0] * n] * (cs - 1)
+            out.append(enc_case(f"flush dial bs={bs} cs={cs} r={r}", cfg, (0x0100 + i,) * cs, dsubs))
+            i += 1
+    for bs, cs in FLUSH_RAW:
+        spl, g = enc_template(bs)
+        rng = np.random.default_rng(950 + bs + cs)
+        for ragged in (0, bs // 2 + 1):
+            cfg = Cfg(bs, cs, ragged == 0, 0)
+            nsub = (64 // g) * (5 if spl == 16 else 7) - cs
+            dsubs = [noise(rng, bs) for _ in range(nsub)] + [noise(rng, ragged) for _ in range(cs if ragged else 0)]
+            for c in range(cs):
+                dsubs[c] = [0] + dsubs[c][1:]
+            out.append(enc_case(f"flush all raw bs={bs} cs={cs} ragged={ragged}", cfg, (0x0100 + i,) * cs, dsubs,
+                                ["raw"] * len(dsubs)))
+            i += 1
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_shapes
+# ---------------------------------------------------------------------------------------------------------------
+
+SHAPE_BS = (1, 7, 8, 9, 16, 17, 29, 32, 33, 64, 65, 99, 128, 129, 200, 256, 257, 500, 512)
+SHAPE_CFG = ((True, 0), (False, 3), (True, 6))
+
+
+def wander(rng, cfg: Cfg, n: int, px: int, scale: int) -> Tuple[List[int], int]:
+    """n zig-zag deltas of a random walk of the given scale that stays inside the pixel range."""
+    top = (1 << (16 - cfg.ulsb)) - 1
+    d = []
+    for step in (rng.normal(0, scale, n) if scale else np.zeros(n)):
+        p = min(top, max(0, px + min(32767, max(-32768, int(round(step))))))
+        d.append(zz(p - px))
+        px = p
+    return d, px
+
+
+def shape_ns(bs: int, cs: int) -> List[int]:
+    chunk = bs * cs
+    ns = {0, cs, 2 * cs, chunk - cs, chunk, chunk + cs} | {3 * chunk + cs * r for r in (1, 2, bs - 1) if 0 < r < bs}
+    return sorted(x for x in ns if x >= 0)
+
+
+@functools.lru_cache(maxsize=None)
+def enc_shapes() -> List[Case]:
+    """Every block size at which the kernel template, the lane count or the ragged handling changes, one and two
+    components, three pixel formats; stream lengths 0, cs, 2 cs, one chunk and cs either way, and three chunks
+    with a ragged last one of 1, 2 and bs - 1 samples.  Random walks whose scale changes per sub-block (zero,
+    every fs, raw)."""
+    out = []
+    i = 0
+    for bs in SHAPE_BS:
+        for cs in (1, 2):
+            for big, ulsb in SHAPE_CFG:
+                cfg = Cfg(bs, cs, big, ulsb)
+                rng = np.random.default_rng(5000 + 7 * bs + 3 * cs + ulsb)
+                top = 1 << (16 - ulsb)
+                for n in shape_ns(bs, cs):
+                    i += 1
+                    per = n // cs
+                    first = [int(rng.integers(0, top)) for _ in range(cs)]
+                    px, dsubs = list(first), []
+                    for lo in range(0, per, bs):
+                        for c in range(cs):
+                            scale = (0, 1, 3, 40, 700, top // 3, 2, 9000)[int(rng.integers(0, 8))]
+                            d = wander(rng, cfg, min(bs, per - lo), px[c], min(scale, top))[0]
+                            if lo == 0:
+                                d[0] = 0
+                            d, px[c] = _rewalk(cfg, px[c], d)
+                            dsubs.append(d)
+                    out.append(enc_case(f"shape {cfg} n={n}", cfg, tuple(first) if n else (0,) * cs, dsubs))
+    return out
+
+
+def _rewalk(cfg: Cfg, px: int, d: List[int]) -> Tuple[List[int], int]:
+    """The deltas clamped so that the walk from px stays in range, and its end."""
+    top = (1 << (16 - cfg.ulsb)) - 1
+    out = []
+    for x in d:
+        p = min(top, max(0, px + unzz(x)))
+        out.append(zz(p - px))
+        px = p
+    return out, px
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_segments
+# ---------------------------------------------------------------------------------------------------------------
+
+SEG_SHORT = ("4", "4cs", "8", "20", "31", "32", "33")  # bits of a short last segment
+SEG_SH = (0, 3, 8, 11, 24, 27, 28, 31)                # o_1 % 32 beside them
+
+
+def _short_last(cfg: Cfg, name: str) -> List[List[int]]:
+    """The chunks of a last segment of that many bits."""
+    bits = 4 * cfg.cs if name == "4cs" else int(name)
+    if bits % (4 * cfg.cs) == 0 and bits <= 8:
+        full = bits // (4 * cfg.cs) - 1
+        return [[0] * cfg.bs] * (cfg.cs * full) + [[0] * 3] * cfg.cs  # (zero chunks, the last ragged)
+    ns = bits - 4 * cfg.cs  # n + s of a ragged fs 0 sub-block (the other component's is zero)
+    n = ns // 2 + 1
+    assert ns > 2 and n < cfg.bs, (cfg, name)
+    return [ones(n, ns - n)] + [[0] * n] * (cfg.cs - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def enc_segments_fields():
+    out = []
+    S = ENC_SEG_MIN
+    i = 0
+    for bs, cs in ((16, 1), (16, 2), (29, 1), (29, 2)):
+        cfg = Cfg(bs, cs, bs == 16, 0)
+        rng = np.random.default_rng(600 + bs + cs)
+        base0 = 16 * cs + 4 * cs * S   # segment 0 of zero sub-blocks
+
+        def seg(extra, raws=False):
+            return dial(cfg, S, extra, rng if raws else None)
+
+        def typical_tail(chunks, ragged):
+            d = []
+            for j in range(chunks * cs):
+                d.append(wander(rng, cfg, bs, 0x4000, (0, 2, 30, 9000)[j % 4])[0])
+            return d + ([wander(rng, cfg, ragged, 0x4000, 5)[0] for _ in range(cs)] if ragged else [])
+
+        def add(what, segs, aim):
+            nonlocal i
+            dsubs = [list(d) for s in segs for d in s]
+            for c in range(cs):
+                dsubs[c][0] = 0
+            # (ulsb 0: the deltas of walks drawn apart are one walk mod 2^16)
+            out.append((f"seg {what} bs={bs} cs={cs}", cfg, (0x4000 + i,) * cs, dsubs, aim))
+            i += 1
+
+        for r in range(32):  # o_1 at every residue, two segments; then o_2, o_3 with three to five
+            e = (r - base0) % 32 + 2 * bs + 2 + 32
+            add(f"o1%32={r} two", [seg(e + 32 * (r % 3) * 3, raws=r % 2 == 1), typical_tail(1 + r % 5, r % bs)], ("o1", r))
+            nseg = 3 + r % 3
+            o_1 = base0 + 2 * bs + 2 + r
+            mids = [seg((r - o_1 - 4 * cs * S) % 32 + 2 * bs + 2 + 32 if k == 1 else 2 * bs + 2 + (5 * r + 7 * k) % 29,
+                        raws=(r + k) % 4 == 0) for k in range(1, nseg - 1)]
+            add(f"o2%32={r} nseg={nseg}", [seg(2 * bs + 2 + r)] + mids + [typical_tail(r % 3, 1 + r % (bs - 1))], ("ok", r))
+        for name in SEG_SHORT:
+            if name == "4" and cs == 2:
+                continue
+            for sh in SEG_SH:
+                e = (sh - base0) % 32 + 2 * bs + 2 + 32
+                add(f"short last {name} sh={sh} two", [seg(e), _short_last(cfg, name)], ("short2", name, sh))
+            for sh in SEG_SH[::3]:
+                e = (sh - base0) % 32 + 2 * bs + 2 + 32
+                add(f"short last {name} sh={sh} minimal middle", [seg(e), seg(0), _short_last(cfg, name)],
+                    ("short3", name, sh))
+                add(f"short last {name} sh={sh} four", [seg(e, raws=True), seg(0), seg(2 * bs + 9), _short_last(cfg, name)],
+                    ("short4", name, sh))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def enc_segments() -> List[Case]:
+    """Streams of more than 16 chunks, which a small batch splits into units of 16 chunks: two to five segments
+    whose lengths zero, fs 0 and raw sub-blocks dial, so that o_1 % 32 and some o_k % 32 (k >= 2) take every
+    residue, middle segments have the minimal 64 cs bits, and the last segment has 4, 4 cs, 8, 20, 31, 32 and 33
+    bits beside o_1 % 32 of 0..31 (L_1 < 32 - sh in many)."""
+    return [enc_case(what, cfg, first, dsubs) for what, cfg, first, dsubs, _ in enc_segments_fields()]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# enc_values
+# ---------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def enc_values() -> List[Case]:
+    """Differences of +-1, +-32767 and -32768, 0 -> 0xFFFF and back, initial values with the high bit set, both
+    byte orders; with ulsb 3 and 15 dirty unused low bits in a sub-block that is otherwise all zero (dropped) and
+    in a raw sub-block (stored as they lie); a raw sub-block followed by Rice and by zero."""
+    out = []
+    for bs, cs in ((16, 1), (128, 1), (32, 2), (29, 2)):
+        for big in (True, False):
+            rng = np.random.default_rng(8000 + bs + cs + big)
+            cfg = Cfg(bs, cs, big, 0)
+            ext = [zz(1), zz(-1), zz(32767), zz(-32768), zz(-32767), zz(1), zz(-1), zz(32767), zz(-32767), 0]
+            for init in (0, 0xFFFF, 0x8000, 0x8001):
+                subs = [[0] * bs] * cs
+                subs += [[ext[(j + 3 * c) % len(ext)] for j in range(bs)] for c in range(cs)]       # (raw)
+                subs += [[zz(1) if j % 2 else zz(-1) for j in range(bs)] for c in range(cs)]        # +-1
+                subs += [[zz(-1)] + [0] * (bs - 1) for c in range(cs)]                              # one step
+                subs += [[zz(32767 if j == 5 else -32768 if j == 9 else -32767 if j == 12 else j % 3 - 1)
+                          for j in range(bs)] for c in range(cs)]                                   # extremes in Rice
+                subs += [[0] * bs] * cs
+                subs += [[zz(-1 if j == 0 else 1 if j == 1 else 0) for j in range(bs)] for c in range(cs)]
+                out.append(enc_case(f"values extremes {cfg} init={init:#06x}", cfg, (init,) * cs, subs))
+            # 0 -> 0xFFFF and back, alone in otherwise zero sub-blocks
+            subs = [[0] * bs] * cs + [[0] * 3 + [zz(-1)] + [0] * (bs - 4)] * cs + [[zz(1)] + [0] * (bs - 1)] * cs
+            out.append(enc_case(f"values 0 to 0xffff and back {cfg}", cfg, (0,) * cs, subs))
+            for ulsb in (3, 15):
+                cfg = Cfg(bs, cs, big, ulsb)
+                top = 1 << (16 - ulsb)
+                hi = top >> 1  # (the pixel's high bit)
+                low = lambda n: [int(x) for x in rng.integers(0, 1 << ulsb, n)]
+                step = [zz(1) if top > 2 else 0] + [0] * (bs - 1)
+                back = [zz(-1) if top > 2 else 0] + [0] * (bs - 1)
+                nz = lambda n: [0] + [int(x) for x in rng.integers(0, 2, n - 1) * (2 if top > 2 else 0)]
+                # dirty zero, a raw sub-block (dirty) then Rice, then zero (dirty), raw then zero, a ragged dirty zero
+                raw_d = [zz(int(x)) for x in rng.integers(-1, 2, bs)] if top > 2 else [0] * bs
+                kinds, subs, dirt = [], [], {}
+                def put(kind, d, dirty=False):
+                    if dirty:
+                        dirt[len(subs)] = low(len(d))
+                    kinds.append(kind if kind != "aim" else aim_kind(d))
+                    subs.append(d)
+                for c in range(cs):
+                    put("zero", [0] * bs, dirty=True)
+                for c in range(cs):
+                    # (13-bit pixels: raw needs every delta in [3 * 2^12, 2^14), the equal-cost step 13 -> 14)
+                    put("raw", [0] * bs if top == 2 else ([zz(-6200), zz(6200)] * bs)[:bs], dirty=True)
+                if top == 2:  # (one pixel bit: only the dirt makes a sub-block raw, so none is)
+                    kinds[-cs:] = ["zero"] * cs
+                for c in range(cs):
+                    put("aim", step)
+                for c in range(cs):
+                    put("zero", [0] * bs, dirty=True)
+                for c in range(cs):
+                    put("aim", back)
+                for c in range(cs):
+                    put("raw" if top > 2 else "zero", [0] * bs if top == 2 else ([zz(6200), zz(-6200)] * bs)[bs % 2 == 0:][:bs])
+                for c in range(cs):
+                    put("zero", [0] * bs)
+                for c in range(cs):
+                    put("zero", [0] * 5, dirty=True)
+                for init in ((6200, 6201) if top > 2 else (1, 0)):
+                    out.append(enc_case(f"values dirt {cfg} init={init:#06x}", cfg, (init,) * cs, subs, kinds, dirt))
+    return out
+
+
+ENC_FAMILIES = {"enc_split_start": enc_split_start, "enc_split_walk": enc_split_walk,
+                "enc_emit_paths": enc_emit_paths, "enc_flush_edges": enc_flush_edges, "enc_shapes": enc_shapes,
+                "enc_segments": enc_segments, "enc_values": enc_values}
