@@ -23,6 +23,8 @@ RPP_HIP_ERROR = -5
 RPP_INTERNAL_ERROR = -6
 RPP_CHECKSUM_MISMATCH = -7
 RPP_CORRUPT_INPUT = -8
+RPP_BAD_CHUNK = -9
+RPP_CHUNK_HOLE = 0xFFFFFFFF  # rpp_chunk.block of a hole
 
 RPP_DECODE_AUTO = 0
 RPP_DECODE_FUSED = 1
@@ -41,6 +43,7 @@ STATUS_NAMES = {
     RPP_INTERNAL_ERROR: "INTERNAL_ERROR",
     RPP_CHECKSUM_MISMATCH: "CHECKSUM_MISMATCH",
     RPP_CORRUPT_INPUT: "CORRUPT_INPUT",
+    RPP_BAD_CHUNK: "BAD_CHUNK",
 }
 
 # Every symbol declared in include/ricepp_amd.h.
@@ -164,6 +167,10 @@ EXPORTED_SYMBOLS = (
     "rpp_incompressible_workspace_bytes_long",
     "rpp_incompressible_scan_batch_long",
     "rpp_incompressible_host_scan_long",
+    "rpp_extract_tile_bytes",
+    "rpp_extract_workspace_bytes",
+    "rpp_extract_gather_batch",
+    "rpp_extract_host_gather",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -277,6 +284,12 @@ class RppSegmentConfig(C.Structure):
 
 class RppSegmentScanResult(C.Structure):
     _fields_ = [("count", C.c_uint64), ("status", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class RppChunk(C.Structure):
+    """``rpp_chunk``: a file's chunk row (block ``RPP_CHUNK_HOLE``: a hole of ``size`` bytes)."""
+
+    _fields_ = [("block", C.c_uint32), ("offset", C.c_uint32), ("size", C.c_uint64)]
 
 
 class RppOrderStats(C.Structure):
@@ -556,6 +569,14 @@ def lib() -> C.CDLL:
         L.rpp_incompressible_host_scan_long.argtypes = [P, P, P, U32, P, U32, C.c_double, U32, U32, U32, U32, P, P, P, P,
                                                         P, P]
         L.rpp_incompressible_host_scan_long.restype = C.c_int
+        L.rpp_extract_tile_bytes.argtypes = []
+        L.rpp_extract_tile_bytes.restype = U64
+        L.rpp_extract_workspace_bytes.argtypes = [U64, U32, U64]
+        L.rpp_extract_workspace_bytes.restype = U64
+        L.rpp_extract_gather_batch.argtypes = [P, U64, P, P, U32, P, P, U64, P, U32, P, U64, P, P, U64, P]
+        L.rpp_extract_gather_batch.restype = C.c_int
+        L.rpp_extract_host_gather.argtypes = [P, U64, P, P, U32, P, P, U64, P, U32, P, U64, P]
+        L.rpp_extract_host_gather.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

@@ -332,6 +332,80 @@ def decompress_sections(image: bytes, verify: int = 1, device="cuda") -> List[by
     return out  # type: ignore[return-value]
 
 
+def decode_sections_device(image: bytes, verify: int = 1, device="cuda"):
+    """What :func:`decompress_sections` does (the same sections, the same integrity check, the same errors), but the
+    decoded blocks stay on the device: ``(blocks, block_offsets, block_sizes)`` -- one uint8 device buffer on a
+    16-byte boundary, padded to a multiple of 16 bytes, in which block b is ``blocks[block_offsets[b] :
+    block_offsets[b] + block_sizes[b]]`` (int64 device tensors; every block starts on a 16-byte boundary), ready for
+    ``extract.gather_files``.  The ricepp, LZ4 and ZSTD batches decode straight into their places in that buffer;
+    a NONE section is a device-to-device copy out of the uploaded image.  FLAC, lzma and brotli sections raise."""
+    dev = torch.device(device)
+    image = bytes(image)
+    secs, bad_at = S.walk(image)
+    if verify not in (0, 1, 2):
+        raise ValueError("verify must be 0, 1 or 2")
+    if bad_at is not None and not verify:
+        raise RuntimeError(S.INTEGRITY_ERROR)
+    padded = np.zeros(len(image) + 64, np.uint8)  # (the decoder reads whole 16-byte granules)
+    padded[:len(image)] = np.frombuffer(image, np.uint8)
+    d_image = torch.from_numpy(padded).to(dev)
+    if verify and (secs or bad_at is not None):
+        offsets = [at for at, _ in secs] + ([bad_at] if bad_at is not None else [])
+        status = S.sections_verify_batch(d_image, len(image), offsets, verify)
+        if int(status.abs().sum().item()) != 0:
+            raise RuntimeError(S.INTEGRITY_ERROR)
+    sizes = [0] * len(secs)
+    none_secs, lz4_secs, zstd_secs, groups = [], [], [], {}
+    for i, (at, h) in enumerate(secs):
+        at, length = at + S.HEADER_BYTES, int(h.length)
+        if h.type == S.SECTION_TYPE_BLOCK and h.compression == Z.COMPRESSION_TYPE_NONE:
+            none_secs.append((i, at))
+            sizes[i] = length
+        elif h.type == S.SECTION_TYPE_BLOCK and h.compression in (Z.COMPRESSION_TYPE_LZ4, Z.COMPRESSION_TYPE_LZ4HC):
+            lz4_secs.append((i, at + Z.FRAME_BYTES, length - Z.FRAME_BYTES))
+            sizes[i] = Z.parse_frame(image[at:at + length])[0]
+        elif h.type == S.SECTION_TYPE_BLOCK and h.compression == ZS.COMPRESSION_TYPE_ZSTD:
+            frame = ZS.ZstdBlockDecompressor(image[at:at + length], dev)
+            nblocks = ZS.count_blocks(frame.data)
+            ZS.raise_decode_status(min(nblocks, 0))
+            zstd_secs.append((i, at, length, nblocks))
+            sizes[i] = frame.uncompressed_size()
+        elif h.type == S.SECTION_TYPE_BLOCK and h.compression == COMPRESSION_TYPE_RICEPP:
+            dec = RiceppBlockDecompressor(image[at:at + min(length, 64)], dev)
+            hdr_len = min(length, 64) - len(dec.data)
+            groups.setdefault(dec.config, []).append((i, at + hdr_len, length - hdr_len))
+            sizes[i] = dec.uncompressed_size()
+        else:
+            raise RuntimeError(f"section {h.number}: not a ricepp, lz4, zstd or uncompressed block "
+                               f"(type {h.type}, compression {h.compression})")
+    offs, total = Z._layout(sizes)
+    blocks = torch.zeros(max(total, 16), dtype=torch.uint8, device=dev)
+    pending = []  # (status tensor, how its entries raise)
+    for i, at in none_secs:
+        blocks[int(offs[i]):int(offs[i]) + sizes[i]] = d_image[at:at + sizes[i]]
+    if lz4_secs:
+        idx = [i for i, _, _ in lz4_secs]
+        _, _, st = Z.decode_batch(d_image, [at for _, at, _ in lz4_secs], [n for _, _, n in lz4_secs],
+                                  [sizes[i] for i in idx], out=blocks, out_offsets=offs[idx])
+        pending.append((st, Z.raise_decode_status))
+    if zstd_secs:
+        idx = [i for i, _, _, _ in zstd_secs]
+        _, _, st = ZS.decode_batch(d_image, [at for _, at, _, _ in zstd_secs], [n for _, _, n, _ in zstd_secs],
+                                   [sizes[i] for i in idx], sum(b for _, _, _, b in zstd_secs), out=blocks,
+                                   out_offsets=offs[idx])
+        pending.append((st, ZS.raise_decode_status))
+    for cfg, rows in groups.items():
+        idx = [i for i, _, _ in rows]
+        _, st = decode_batch(cfg, d_image, [at for _, at, _ in rows], [n for _, _, n in rows],
+                             [sizes[i] // 2 for i in idx], out=blocks.view(torch.int16), out_offsets=offs[idx] // 2)
+        pending.append((st, _raise_status))
+    torch.cuda.current_stream().synchronize()
+    for st, raise_status in pending:
+        for s in st.cpu().numpy():
+            raise_status(int(s))
+    return blocks, torch.from_numpy(offs).to(dev), torch.as_tensor(np.asarray(sizes, np.int64), device=dev)
+
+
 class NullBlockCompressor:
     """``null_block_compressor`` (src/compression/null.cpp): compression type NONE, the bytes as they are."""
 

@@ -1235,6 +1235,51 @@ int rpp_incompressible_host_scan_long(const uint8_t* in, const uint64_t* in_offs
                                       uint32_t long_mode, uint64_t* sizes, uint32_t* verdicts, uint64_t* totals,
                                       uint64_t* frag_rows, uint32_t* frag_count, int32_t* status);
 
+/*
+ * File extraction: chunks of decoded blocks become files (the readers that walk every file's chunk list,
+ * src/utility/filesystem_extractor.cpp and dwarfsck --checksum, tools/src/dwarfsck_main.cpp do_checksum).  A file is
+ * a list of chunks (thrift/metadata.thrift, `chunk`); a chunk row is this project's own: `size` is 64-bit because a
+ * row with block == RPP_CHUNK_HOLE is a hole, `size` zero bytes without a source.
+ *   blocks      block b is d_blocks[d_block_offsets[b] .. + d_block_sizes[b]), any alignment inside a buffer of
+ *               blocks_bytes bytes whose address is 16-aligned and whose allocation is padded to a multiple of 16:
+ *               loads are aligned and stay inside [0, round_up(blocks_bytes, 16)).
+ *   files       CSR: file f holds the chunks d_file_first_chunk[f] .. d_file_first_chunk[f + 1] (nfiles + 1 entries
+ *               from 0 to nchunks that do not decrease); chunk c's bytes go to d_out[d_chunk_dst[c] .. + size).
+ *               d_chunk_dst has nchunks + 1 entries and does not decrease: the exclusive scan of the chunk sizes laid
+ *               over the files' places in d_out (its last entry is the end of the last chunk).  d_out is 16-aligned.
+ *   bad chunk   a chunk is bad when block >= nblocks and it is no hole; when offset + size > d_block_sizes[block]
+ *               (in 64 bits) or the block itself passes blocks_bytes; when d_chunk_dst[c] + size > out_bytes or
+ *               > d_chunk_dst[c + 1] (it would run into its neighbour).  Its file's d_file_status is RPP_BAD_CHUNK
+ *               and its destination bytes are left as they are; every other chunk, of the same file too, is copied.
+ *   d_file_status  nfiles entries, RPP_OK or RPP_BAD_CHUNK; the call writes every one.
+ * Bytes of d_out that no chunk covers are not written.  The 16-aligned workspace holds
+ * rpp_extract_workspace_bytes(nchunks, nfiles, out_bytes) bytes and needs no initialisation; a smaller one, a null
+ * pointer where bytes are needed, a misaligned d_blocks, d_out or workspace, or nchunks > 0 with nfiles == 0 is
+ * RPP_INVALID_ARGUMENT.  nchunks == 0 clears the statuses and is RPP_OK.  rpp_extract_tile_bytes is the gather
+ * kernel's tile of output bytes (for tests and tools).  rpp_extract_host_gather is the definition (host memory, any
+ * alignment; it also refuses a file table that decreases or does not span 0 .. nchunks, where the kernels clamp); its
+ * rules are at the top of dwarfs_amd/csrc/extract/extract_host.cpp.  Where d_chunk_dst decreases, which bytes of
+ * d_out the device call writes is unspecified, but no store leaves a good chunk's destination and no load its block.
+ */
+#define RPP_BAD_CHUNK (-9)
+#define RPP_CHUNK_HOLE 0xFFFFFFFFu
+typedef struct rpp_chunk {
+  uint32_t block;
+  uint32_t offset;
+  uint64_t size;
+} rpp_chunk;
+uint64_t rpp_extract_tile_bytes(void);
+uint64_t rpp_extract_workspace_bytes(uint64_t nchunks, uint32_t nfiles, uint64_t out_bytes);
+int rpp_extract_gather_batch(const uint8_t* d_blocks, uint64_t blocks_bytes, const uint64_t* d_block_offsets,
+                             const uint64_t* d_block_sizes, uint32_t nblocks, const rpp_chunk* d_chunks,
+                             const uint64_t* d_chunk_dst, uint64_t nchunks, const uint64_t* d_file_first_chunk,
+                             uint32_t nfiles, uint8_t* d_out, uint64_t out_bytes, int32_t* d_file_status,
+                             void* d_workspace, uint64_t workspace_bytes, void* stream);
+int rpp_extract_host_gather(const uint8_t* blocks, uint64_t blocks_bytes, const uint64_t* block_offsets,
+                            const uint64_t* block_sizes, uint32_t nblocks, const rpp_chunk* chunks,
+                            const uint64_t* chunk_dst, uint64_t nchunks, const uint64_t* file_first_chunk,
+                            uint32_t nfiles, uint8_t* out, uint64_t out_bytes, int32_t* file_status);
+
 #ifdef __cplusplus
 }
 #endif
