@@ -8,8 +8,12 @@
 // by frames written field by field (tests/flac_build.py, tests/flac_cases.py)
 // that an independent RFC 9639 reader (tests/flac_ref.py) and the CPU
 // restatement decode alike; the encoder is pinned to the format by that
-// reader, not bit-for-bit to libFLAC's encoder choices (the reference holds no
-// FLAC fixture).  The decoder accepts every frame kind RFC 9639 defines (constant,
+// reader, and its choices to a rule-by-rule model (tests/flac_enc_model.py on
+// the inputs of tests/flac_enc_cases.py): byte for byte at levels 0-2, where
+// every step is integer, and from level 3 given the coefficients it wrote
+// (orders, precision, the Rice plan of the residuals they imply, LPC only
+// where strictly cheaper).  It is still not pinned to libFLAC's encoder
+// choices (the reference holds no FLAC fixture).  The decoder accepts every frame kind RFC 9639 defines (constant,
 // verbatim, fixed and LPC subframes, wasted bits, both Rice methods, escape
 // partitions, the four channel assignments, any block size code), so it reads
 // libFLAC's streams; the encoder writes constant, verbatim, fixed and LPC
@@ -261,7 +265,7 @@ __device__ __forceinline__ int64_t lpc_res(const EncShared& sh, const int32_t* q
 // predictor order, per partition k = floor(log2(mean u)); the cheapest order
 // and method in bpo / bmethod, its parameters in sh.kt[2^bpo - 1 + p].
 // Returns the residual's bits (its 6-bit header included), or ~0 when a
-// residual does not fit 32 bits.
+// residual is outside -2^31 < r <= 2^31 - 1 (RFC 9639 9.2.7.3).
 template <class Res>
 __device__ uint64_t rice_plan(EncShared& sh, uint32_t bs, uint32_t order, uint32_t po_cap, Res&& res,
                               uint32_t& bpo, uint32_t& bmethod) {
@@ -287,7 +291,8 @@ __device__ uint64_t rice_plan(EncShared& sh, uint32_t bs, uint32_t order, uint32
         acc = 0;
       }
       const uint64_t u = fold(res(i));
-      bad |= u >> 32 ? 1u : 0u;
+      // (RFC 9639 9.2.7.3 excludes the most negative 32-bit value: its fold, 2^32 - 1, does not fit either)
+      bad |= u >= 0xFFFFFFFFull ? 1u : 0u;
       sh.ures[i] = (uint32_t)u;
       acc += u;
     }
@@ -457,7 +462,7 @@ __device__ SubPlan plan_subframe(EncShared& sh, const FlacEncParams& prm, uint32
 #pragma unroll
     for (uint32_t o = 0; o <= 4; ++o) {
       if (i < o) continue;
-      if (r[o] < INT32_MIN || r[o] > INT32_MAX) bad |= 1u << o;
+      if (r[o] <= INT32_MIN || r[o] > INT32_MAX) bad |= 1u << o;  // (9.2.7.3: -2^31 itself is excluded)
       sabs[o] += (uint64_t)(r[o] < 0 ? -r[o] : r[o]);
     }
   }

@@ -15,9 +15,10 @@ the other way (rpp_flac_decode, rpp_pcm_pack).
 
 FLAC decode is pinned to libFLAC 1.3.3 by the three RFC 9639 Appendix D
 streams and their MD5s (tests/golden/flac_rfc9639.json); the encoder is pinned
-to the format by an independent RFC 9639 reader (tests/flac_ref.py); it is not
-pinned bit-for-bit to libFLAC's encoder choices, and this remains unpinned:
-libFLAC's model search (LPC orders, precision, apodization) decides its bytes,
+to the format by an independent RFC 9639 reader (tests/flac_ref.py) and its
+choices to a rule-by-rule model (tests/flac_enc_model.py: byte for byte at
+levels 0-2, from level 3 given the coefficients it wrote); it is not pinned to
+libFLAC's encoder choices, and this remains unpinned: libFLAC's model search (LPC orders, precision, apodization) decides its bytes,
 and this encoder writes valid FLAC with fixed and LPC predictors chosen by its
 own search.  The decoder reads every frame kind RFC 9639 defines.  ``level`` selects libFLAC's preset limits (levels 0-2 fixed
 predictors only, 3 LPC up to order 6, 4-6 up to 8, 7-8 up to 12) and

@@ -272,8 +272,12 @@ class _Bits:
             raise FlacError("non-zero padding bits before the CRC-16")
 
 
-def _residual(r: _Bits, bs: int, order: int, keep: bool):
-    """The residual section (section 9.2.7): bs - order values, or None when not kept."""
+_RES_MIN = -(1 << 31)  # excluded by section 9.2.7.3: "a 32-bit signed integer, excluding the most negative value"
+
+
+def _residual(r: _Bits, bs: int, order: int, keep: bool, plan: dict | None = None):
+    """The residual section (section 9.2.7): bs - order values, or None when not kept.  A residual of -2^31,
+    Rice coded or in an escaped partition, is refused whether the values are kept or not (section 9.2.7.3)."""
     method = r.read(2)
     if method > 1:
         raise FlacError("residual coding method is reserved")
@@ -282,33 +286,60 @@ def _residual(r: _Bits, bs: int, order: int, keep: bool):
     if bs % (1 << po) or (bs >> po) < order:
         raise FlacError(f"partition order {po} does not fit block size {bs}, predictor order {order}")
     out = [] if keep else None
+    params = []
     for part in range(1 << po):
         count = (bs >> po) - (order if part == 0 else 0)
         k = r.read(pbits)
         if k == (1 << pbits) - 1:  # escape: raw signed values
             w = r.read(5)
+            params.append(("esc", w))
             if keep:
-                out.extend(r.signed(w) for _ in range(count))
+                vals = [r.signed(w) for _ in range(count)]
+                if _RES_MIN in vals:  # (out of reach of the 5-bit width field, at most 31 bits; kept for the rule)
+                    raise FlacError("an escaped residual of -2^31 (section 9.2.7.3)")
+                out.extend(vals)
             else:
                 r.skip(w * count)
         else:
+            params.append(k)
             unary, read = r.unary, r.read
+            worst = 0xFFFFFFFF  # the folded -2^31
             if keep:
                 for _ in range(count):
                     u = (unary() << k) | read(k)
+                    if u == worst:
+                        raise FlacError("a residual of -2^31 (section 9.2.7.3)")
                     out.append(-(u >> 1) - 1 if u & 1 else u >> 1)
             else:
                 for _ in range(count):
-                    unary()
-                    read(k)
+                    if (unary() << k) | read(k) == worst:
+                        raise FlacError("a residual of -2^31 (section 9.2.7.3)")
+    if plan is not None:
+        plan.update(partition_order=po, method=method, params=tuple(params))
     return out
 
 
 _FIXED = ((), (1,), (2, -1), (3, -3, 1), (4, -6, 4, -1))
 
 
-def _subframe(r: _Bits, bs: int, bits: int, keep: bool):
+class SubframePlan(NamedTuple):
+    """What a subframe's fields say about how it was coded (walk_plans)."""
+    kind: str             # "constant", "verbatim", "fixed", "lpc"
+    order: int
+    wasted: int
+    partition_order: int  # fixed and lpc; else 0
+    method: int           # 0: 4-bit Rice parameters, 1: 5-bit
+    params: tuple         # per partition the Rice parameter k, or ("esc", width)
+    precision: int        # lpc; else 0
+    shift: int
+    coefs: tuple          # lpc: newest sample first
+    bits: int             # the subframe's length in the stream
+
+
+def _subframe(r: _Bits, bs: int, bits: int, keep: bool, plans: list | None = None):
     """One subframe of ``bits``-bit samples (section 9.2)."""
+    start = r.bit_pos()
+    plan = {} if plans is not None else None
     if r.read(1):
         raise FlacError("subframe padding bit is set")
     kind = r.read(6)
@@ -340,7 +371,11 @@ def _subframe(r: _Bits, bs: int, bits: int, keep: bool):
             coef = [r.signed(prec) for _ in range(order)]
         else:
             shift, coef = 0, _FIXED[order]
-        res = _residual(r, bs, order, keep)
+        res = _residual(r, bs, order, keep, plan)
+        if plan is not None:
+            plan.update(order=order)
+            if kind >= 32:
+                plan.update(precision=prec, shift=shift, coefs=tuple(coef))
         out = None
         if keep:
             out = warm
@@ -355,6 +390,11 @@ def _subframe(r: _Bits, bs: int, bits: int, keep: bool):
                     out.append(e + (acc >> shift))
     else:
         raise FlacError(f"subframe type {kind} is reserved")
+    if plans is not None:
+        name = "constant" if kind == 0 else "verbatim" if kind == 1 else "fixed" if kind < 32 else "lpc"
+        plans.append(SubframePlan(name, plan.get("order", 0), wasted, plan.get("partition_order", 0),
+                                  plan.get("method", 0), plan.get("params", ()), plan.get("precision", 0),
+                                  plan.get("shift", 0), plan.get("coefs", ()), r.bit_pos() - start))
     if keep:
         lo, hi = -(1 << (b - 1)), (1 << (b - 1)) - 1
         if any(v < lo or v > hi for v in out):
@@ -378,9 +418,11 @@ class Frame(NamedTuple):
     samples: object  # per-channel lists after stereo reconstruction (decode), else None
 
 
-def frame_at(data: bytes, pos: int, channels: int, bits: int, keep: bool = False, first_sample: int = 0) -> Frame:
+def frame_at(data: bytes, pos: int, channels: int, bits: int, keep: bool = False, first_sample: int = 0,
+             plans: list | None = None) -> Frame:
     """The frame at byte ``pos`` of a ``channels`` x ``bits`` stream, whatever its number: header, subframes,
-    padding, CRC-16.  Raises FlacError where it does not parse; CRC mismatches are reported in the result."""
+    padding, CRC-16.  Raises FlacError where it does not parse; CRC mismatches are reported in the result.
+    ``plans``: a list that receives one SubframePlan per subframe, in stream order."""
     h = parse_header(data, pos)
     if h.size_code and _SIZES[h.size_code] != bits:
         raise FlacError(f"frame sample size {_SIZES[h.size_code]} but STREAMINFO says {bits}")
@@ -391,7 +433,7 @@ def frame_at(data: bytes, pos: int, channels: int, bits: int, keep: bool = False
     subs = []
     for ch in range(chans):
         side = (h.assignment == 8 and ch == 1) or (h.assignment == 9 and ch == 0) or (h.assignment == 10 and ch == 1)
-        subs.append(_subframe(r, h.blocksize, bits + (1 if side else 0), keep))
+        subs.append(_subframe(r, h.blocksize, bits + (1 if side else 0), keep, plans))
     r.align()
     end = r.bit_pos() >> 3
     if end + 2 > len(data):
@@ -416,14 +458,17 @@ def frame_at(data: bytes, pos: int, channels: int, bits: int, keep: bool = False
                  first_sample, subs if keep else None)
 
 
-def _frames(stream: bytes, info: StreamInfo, keep: bool):
+def _frames(stream: bytes, info: StreamInfo, keep: bool, plans: list | None = None):
     stream = bytes(stream)
     pos, done, frames, variable = info.frames_at, 0, [], None
     total = info.total_samples
     while (done < total) if total else (pos < len(stream)):
         if pos >= len(stream):
             raise FlacError(f"stream ends after {done} of {total} samples")
-        f = frame_at(stream, pos, info.channels, info.bits, keep, done)
+        sub_plans = [] if plans is not None else None
+        f = frame_at(stream, pos, info.channels, info.bits, keep, done, sub_plans)
+        if plans is not None:
+            plans.append(sub_plans)
         if variable is None:
             variable = f.variable
         elif variable != f.variable:
@@ -454,6 +499,13 @@ def walk_frames(stream: bytes, info: StreamInfo | None = None) -> list:
     STREAMINFO maximum, or below the minimum on any frame but the last.  CRC mismatches are reported in the
     frames (crc8_ok, crc16_ok), not raised."""
     return _frames(stream, info or parse_streaminfo(stream), False)
+
+
+def walk_plans(stream: bytes, info: StreamInfo | None = None) -> tuple:
+    """(frames, plans): walk_frames' result and, per frame, one SubframePlan per subframe in stream order (for a
+    stereo assignment: the two coded channels, as the assignment names them)."""
+    plans = []
+    return _frames(stream, info or parse_streaminfo(stream), False, plans), plans
 
 
 def decode(stream: bytes) -> list:

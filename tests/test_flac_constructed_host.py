@@ -70,11 +70,18 @@ def test_valid_case_on_both_cpu_readers(name, bits):
         c.check(st, bits)
     info = R.parse_streaminfo(st.data)
     assert (info.channels, info.bits, info.total_samples, info.frames_at) == (st.channels, bits, st.total, 42)
-    frames = R.walk_frames(st.data, info)
-    assert [(f.pos, f.length) for f in frames] == st.frames
-    assert [f.blocksize for f in frames] == st.blocksizes
-    assert all(f.crc8_ok and f.crc16_ok for f in frames)
-    assert R.decode(st.data) == st.samples
+    if c.wide == "min":
+        # a residual of -2^31: the RFC reader enforces section 9.2.7.3; the restatement (and the GPU decoder,
+        # test_gpu_flac_constructed.py) still decode the samples, which fit their width
+        for reader in (R.walk_frames, R.decode):
+            with pytest.raises(R.FlacError, match="9.2.7.3"):
+                reader(st.data)
+    else:
+        frames = R.walk_frames(st.data, info)
+        assert [(f.pos, f.length) for f in frames] == st.frames
+        assert [f.blocksize for f in frames] == st.blocksizes
+        assert all(f.crc8_ok and f.crc16_ok for f in frames)
+        assert R.decode(st.data) == st.samples
     status, y, ch, b = F.decode(st.data, len(st.samples))
     assert status == F.OK and (ch, b) == (st.channels, bits)
     assert np.array_equal(y, as_int32(st.samples))
@@ -84,16 +91,23 @@ def test_valid_case_on_both_cpu_readers(name, bits):
 
 def test_the_widest_residuals_on_the_cpu_readers():
     """Family h under allow_wide: a residual of -2^31 (which RFC 9639 section 9.2.7.3 excludes: the range is
-    that of a 32-bit one's complement integer) and one of 2^31.  Neither CPU reader enforces the residual rule;
-    both decode the samples, which fit their width.  The GPU test requires the same of the codec."""
+    that of a 32-bit one's complement integer) and one of 2^31.  The RFC reader refuses the first by that
+    section and, like the restatement, decodes the second; the restatement enforces neither and decodes the
+    samples, which fit their width.  The GPU test requires the same of the codec."""
     wide = [c for c in K.CASES if c.wide]
-    assert len(wide) == 4 and all(c.wide == "ok" for c in wide)
+    assert sorted(c.wide for c in wide) == ["min", "min", "ok", "ok"]
+    assert {c.name for c in wide if c.wide == "min"} == {"h_res_min_32", "h_res_min_16"}
     for c in wide:
         for bits in c.widths:
             st = K.built(c.name, bits)
             sub = st.marks[0][1]
             assert sub.params == [("rice", 30 if bits == 32 else 28)]
-            assert R.decode(st.data) == st.samples and F.decode(st.data, len(st.samples))[0] == F.OK
+            assert F.decode(st.data, len(st.samples))[0] == F.OK
+            if c.wide == "min":
+                with pytest.raises(R.FlacError, match="9.2.7.3"):
+                    R.decode(st.data)
+            else:
+                assert R.decode(st.data) == st.samples
 
 
 @pytest.mark.parametrize("name,bits", BAD)

@@ -91,7 +91,7 @@ def test_gpu_decodes_every_oracle_stream(name, channels, bits):
         assert FL.decompress(block) == want, (name, blocksize)
 
 
-def test_gpu_encoder_kinds():
+def test_gpu_encoder_kinds(tmp_path):
     """Silence (constant subframes), low bits always zero (wasted bits), one channel constant and one not,
     a frame of white noise (verbatim), a ragged last frame -- round trip and the oracle's decode."""
     rng = np.random.default_rng(5)
@@ -113,9 +113,10 @@ def test_gpu_encoder_kinds():
         import os
         import subprocess
         import sys
-        open("/tmp/flac_kinds.bin", "wb").write(d.stream)
+        dump = tmp_path / "flac_kinds.bin"
+        dump.write_bytes(d.stream)
         trace = subprocess.run([sys.executable, "-c", "import sys; sys.path.insert(0, '.'); from oracle import flac as F; "
-                                "F.decode(open('/tmp/flac_kinds.bin','rb').read(), %d)" % x.size],
+                                "F.decode(open(%r,'rb').read(), %d)" % (str(dump), x.size)],
                                env={**os.environ, "FO_TRACE": "1"}, capture_output=True, text=True).stderr
         raise AssertionError(f"{bad.size} samples differ, first {bad[:8].tolist()}: oracle {y[bad[:8]].tolist()} "
                              f"want {x[bad[:8]].tolist()}\n{trace[:3000]}")
