@@ -171,6 +171,10 @@ EXPORTED_SYMBOLS = (
     "rpp_extract_workspace_bytes",
     "rpp_extract_gather_batch",
     "rpp_extract_host_gather",
+    "rpp_digest_algo",
+    "rpp_digest_bytes",
+    "rpp_digest_batch",
+    "rpp_digest_host",
 )
 
 RPP_HASH_XXH3_64 = 0
@@ -577,6 +581,14 @@ def lib() -> C.CDLL:
         L.rpp_extract_gather_batch.restype = C.c_int
         L.rpp_extract_host_gather.argtypes = [P, U64, P, P, U32, P, P, U64, P, U32, P, U64, P]
         L.rpp_extract_host_gather.restype = C.c_int
+        L.rpp_digest_algo.argtypes = [C.c_char_p]
+        L.rpp_digest_algo.restype = C.c_int
+        L.rpp_digest_bytes.argtypes = [C.c_int]
+        L.rpp_digest_bytes.restype = C.c_int
+        L.rpp_digest_batch.argtypes = [C.c_int, P, P, P, P, U32, P, P]
+        L.rpp_digest_batch.restype = C.c_int
+        L.rpp_digest_host.argtypes = [C.c_int, P, P, P, P, U32, P]
+        L.rpp_digest_host.restype = C.c_int
         if L.rpp_abi_version() != 1:
             raise RuntimeError("libricepp_amd.so ABI mismatch")
         _lib = L

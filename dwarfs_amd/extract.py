@@ -6,6 +6,8 @@ The reader's two bulk paths -- ``dwarfsextract`` (src/utility/filesystem_extract
 on the device (``block_codec.decode_sections_device``), one gather launch lays every file of a batch contiguously
 into one device buffer (``rpp_extract_gather_batch``; the rules are at the top of csrc/extract/extract_host.cpp),
 and the file digests come from ``dedup.file_hash_batch`` on that buffer without a round trip through the host.
+A checksum name that ``dedup`` does not know (``sha256``, ``md5``, ``sha1``, ...: ``digest.ALGORITHMS``) goes through
+``digest.digest_batch`` instead, on the device or, with ``device="cpu"``, on the host definition.
 
 The caller supplies the chunk tables: the frozen metadata is not parsed here.  A file is a list of :class:`Chunk`
 and :class:`Hole` (a sparse file's hole: ``size`` zero bytes without a source).  A chunk that does not fit its
@@ -24,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import dedup, digest
 from .categorize import Hole
 from .codec import _raise_status, _stream_ptr
 from .dedup import _algo, file_hash_batch
@@ -265,17 +268,37 @@ def batches(file_sizes, max_bytes: int) -> List[Tuple[int, int]]:
     return out
 
 
+def _hash_route(algo: str):
+    """``(digest bytes, batch function)`` of a checksum name: the names of ``dedup.ALGORITHMS`` keep their route
+    through ``dedup.file_hash_batch``, every other name goes to ``digest.digest_batch`` (ValueError if neither
+    module knows it)."""
+    if algo in dedup.ALGORITHMS:
+        return _algo(algo)[1], file_hash_batch
+    return digest.digest_bytes(algo), digest.digest_batch
+
+
 def file_checksums(blocks, block_offsets, block_sizes, table: FileTable, algo: str = "xxh3-128",
                    max_bytes: int = DEFAULT_MAX_BYTES, device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
     """``dwarfsck --checksum=ALGO`` for every file: ``(digests, status)``, a uint8 device tensor [nfiles, digest
     bytes] in DwarFS's digest order (as ``dedup.file_hash_batch``; ``hexdigests`` prints them as dwarfsck does) and
     the int32 gather status per file (the digest of a file with ``RPP_BAD_CHUNK`` is over zeros in the bad chunk's
     place).  Gather, then hash: two passes over the bytes, on the device, in batches of at most ``max_bytes``
-    gathered bytes cut at file boundaries (:func:`batches`)."""
+    gathered bytes cut at file boundaries (:func:`batches`).  The names of ``digest.ALGORITHMS`` that ``dedup`` does
+    not have also run with ``device="cpu"`` (host gather, then ``rpp_digest_host``; everything is on the host)."""
     dev = torch.device(device)
-    if dev.type == "cpu":
+    if dev.type == "cpu" and algo in dedup.ALGORITHMS:
         raise ValueError("file_checksums runs the hash kernels: it needs a GPU device")
-    _, nbytes = _algo(algo)
+    nbytes, hash_batch = _hash_route(algo)
+    if dev.type == "cpu":
+        digests = torch.zeros((table.nfiles, nbytes), dtype=torch.uint8)
+        status = torch.zeros(table.nfiles, dtype=torch.int32)
+        for lo, hi in batches(table.file_sizes, max_bytes):
+            out, offsets, sizes, st = gather_files(blocks, block_offsets, block_sizes, table, dev, lo, hi)
+            status[lo:hi] = st
+            if out.numel() == 0:
+                out = torch.zeros(FILE_ALIGN, dtype=torch.uint8)  # (only empty files: a buffer to point at)
+            hash_batch(out, offsets, sizes, algo, out=digests[lo:hi])
+        return digests, status
     blocks = padded_blocks(blocks.to(dev))
     d_boff, d_bsz = _i64(block_offsets, dev), _i64(block_sizes, dev)
     digests = torch.zeros((table.nfiles, nbytes), dtype=torch.uint8, device=dev)
@@ -284,8 +307,8 @@ def file_checksums(blocks, block_offsets, block_sizes, table: FileTable, algo: s
         plan = plan_gather(table, dev, lo, hi)
         out = torch.zeros(max(plan.out_bytes, 16), dtype=torch.uint8, device=dev)
         gather_into(blocks, d_boff, d_bsz, plan, out, status=status[lo:hi])
-        file_hash_batch(out, plan.file_dst.astype(np.int64), plan.file_sizes.astype(np.int64), algo,
-                        out=digests[lo:hi])
+        hash_batch(out, plan.file_dst.astype(np.int64), plan.file_sizes.astype(np.int64), algo,
+                   out=digests[lo:hi])
     return digests, status
 
 

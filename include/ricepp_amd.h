@@ -1280,6 +1280,57 @@ int rpp_extract_host_gather(const uint8_t* blocks, uint64_t blocks_bytes, const 
                             const uint64_t* chunk_dst, uint64_t nchunks, const uint64_t* file_first_chunk,
                             uint32_t nfiles, uint8_t* out, uint64_t out_bytes, int32_t* file_status);
 
+/*
+ * File digests by name: what `dwarfsck --checksum=ALGO` and `mkdwarfs --file-hash=ALGO` accept beyond the two XXH3
+ * hashes (dwarfs::checksum, src/checksum.cpp: any digest that EVP_get_digestbyname finds).  Thirteen digests are
+ * computed here -- MD5, SHA-1, SHA-224/256/384/512, SHA-512/224, SHA3-224/256/384/512 and unkeyed BLAKE2b-512 and
+ * BLAKE2s-256 with default parameters -- and the three of rpp_file_hash are forwarded.  The enum has a numbering
+ * of its own: a value of one enum means nothing to the other group's calls.  Digests are in each standard's byte
+ * order, which is what EVP_DigestFinal_ex returns.
+ *
+ *   rpp_digest_algo    the enum of a name, or a negative value (NULL too).  OpenSSL's names ("md5", "sha1",
+ *                      "sha224", "sha256", "sha384", "sha512", "sha512-224", "sha512-256", "sha3-224", "sha3-256",
+ *                      "sha3-384", "sha3-512", "blake2b512", "blake2s256") match in any letter case, as
+ *                      EVP_get_digestbyname matches them; "xxh3-64" and "xxh3-128" match exactly, as checksum.cpp
+ *                      compares them.  Host only.
+ *   rpp_digest_bytes   the digest's size in bytes; 0 for a value that is no algorithm.  Host only.
+ *   rpp_digest_batch   the contract of rpp_file_hash_batch: file b = d_data[d_offsets[b], + d_sizes[b]) goes to
+ *                      d_digest[rpp_digest_bytes(algo) * b ..], tightly packed; with d_select (NULL: every file) a
+ *                      file whose byte is 0 is not read and its row is not written.  n == 0 is RPP_OK; an unknown
+ *                      algo, or a null pointer with work to do, is RPP_INVALID_ARGUMENT before anything is launched.
+ *                      One lane per file (the chain of a Merkle-Damgard or sponge hash does not split); whole blocks
+ *                      of a payload on a 16-byte boundary (8 for SHA-3) are read by 16-byte loads, everything else
+ *                      byte by byte.  Files are below 2^61 bytes.
+ *   rpp_digest_host    the definition on host memory, on the same round functions (the padding rules are at the top
+ *                      of dwarfs_amd/csrc/digest/digest_host.cpp).  It has the thirteen and "sha512-256"; the two
+ *                      XXH3 hashes have no host form and are RPP_INVALID_ARGUMENT.
+ */
+enum rpp_digest_id {
+  RPP_DIGEST_MD5 = 0,
+  RPP_DIGEST_SHA1 = 1,
+  RPP_DIGEST_SHA224 = 2,
+  RPP_DIGEST_SHA256 = 3,
+  RPP_DIGEST_SHA384 = 4,
+  RPP_DIGEST_SHA512 = 5,
+  RPP_DIGEST_SHA512_224 = 6,
+  RPP_DIGEST_SHA3_224 = 7,
+  RPP_DIGEST_SHA3_256 = 8,
+  RPP_DIGEST_SHA3_384 = 9,
+  RPP_DIGEST_SHA3_512 = 10,
+  RPP_DIGEST_BLAKE2B512 = 11,
+  RPP_DIGEST_BLAKE2S256 = 12,
+  RPP_DIGEST_XXH3_64 = 13,
+  RPP_DIGEST_XXH3_128 = 14,
+  RPP_DIGEST_SHA512_256 = 15,
+  RPP_DIGEST_COUNT = 16,
+};
+int rpp_digest_algo(const char* name);
+int rpp_digest_bytes(int algo);
+int rpp_digest_batch(int algo, const uint8_t* d_data, const uint64_t* d_offsets, const uint64_t* d_sizes,
+                     const uint8_t* d_select, uint32_t n, uint8_t* d_digest, void* stream);
+int rpp_digest_host(int algo, const uint8_t* data, const uint64_t* offsets, const uint64_t* sizes,
+                    const uint8_t* select, uint32_t n, uint8_t* digest);
+
 #ifdef __cplusplus
 }
 #endif
